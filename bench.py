@@ -9,14 +9,32 @@ the GPUs of the job), bf16 on the wire, compute = hand-written MFMA GEMMs
 bounded to the table's times. One process per GPU; under torchrun every
 rank runs this file. Weak scaling: each GPU keeps its local batch of 16.
 
-The headline is compute-bound by construction (2.8 s of compute against
-~40 ms of all-link collectives at N = 8), so three secondary measurements
-ride along as extra keys of the same JSON line:
+A plain run does only what the headline needs: it sets up, warms up, times
+the K steps (one child process of the native binary per rank), writes the
+step's outputs when ``--dump-outputs DIR`` is given, and prints the line.
+Read off the headline's own report, at no extra cost:
 
 * ``slow_iterations``: per timed iteration of the headline, the slowest
   rank's last collective (its duration), its GPU's sclk at the iteration's
   end and the lowest 5-ms sample inside it, and the power at the end (hwmon);
   ``slow`` lists the iterations over median + 0.1 ms.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last
+step left in the FSDP step's result buffers to ``DIR/<name>.npy`` (float32):
+every unit's reduced gradient shard (``grad_shard_NNN``), the two gather
+buffers (``gathered_params_0/1``: the parameters of units 0 and 1, gathered
+last) and the stand-in GEMM's product (``gemm_product``, C = A.B^T of the
+compute tasks). At most 48 MB in all: a larger buffer is written as a fixed
+sample (blocks of 1024 elements, one per equal stretch of the buffer, at
+offsets hashed from the buffer's name). All buffers are filled from fixed
+seeds, so two runs with the same arguments write the same files.
+
+The headline is compute-bound by construction (2.8 s of compute against
+~40 ms of all-link collectives at N = 8), so with ``--full`` secondary
+measurements, each a run of its own, ride along as extra keys of the same
+JSON line, and at N > 1 the exactness pass of
+the collectives runs before anything is timed:
+
 * ``comm_bound``: the ViT-H/32 fp8 data-parallel proxy (BASELINE config 5,
   model_stats/vit_h_32_float8.txt: 7.13 ms of compute, a 1.26 GB bf16
   gradient all-reduce in 8 buckets) - the one baseline config where
@@ -57,7 +75,7 @@ ride along as extra keys of the same JSON line:
 At N = 1 a "collective" is a local device copy: bus bandwidth is reported
 as null (nccl-tests convention: nothing crosses a link).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (N > 1: torchrun --nproc-per-node N ... bench.py --gpus N ...)
 Prints one JSON line on rank 0.
 """
@@ -805,6 +823,11 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the exactness pass (N > 1) and the secondary "
+                         "blocks (comm_bound, compute_stretch, link_bench, timeline, xgmi, hybrids)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--model", default=DEFAULT_MODEL)
     ap.add_argument("--units", type=int, default=32)
     ap.add_argument("--compute", default="gemm")
@@ -886,6 +909,10 @@ def main() -> int:
     os.environ.setdefault("DLNB_STORE_TIMEOUT", "120")
     # Everything below is native (HIP + RCCL from /opt/rocm); torch is not needed.
     os.environ.setdefault("DLNB_NO_TORCH", "1")
+    # The native build this bench runs (dlnetbench_amd/_lib/libdlnb.so, loaded here; the child binaries link
+    # the same build): a tree that was not built stops here, before anything is timed.
+    from dlnetbench_amd import _native
+    native_build = _native.version()
     budget = _Budget(a.wall_budget_s, a.budget_reserve_s, world, rank)
     ph = _Phases()
     on_gpu = a.backend in ("auto", "rccl", "xgmi")
@@ -893,7 +920,7 @@ def main() -> int:
     # (every rank gets the same all-reduced verdict, so all ranks take the
     # same decisions below)
     exact: Dict[str, Any] = {}
-    if a.exact == "on" or (a.exact == "auto" and world > 1):
+    if a.full and (a.exact == "on" or (a.exact == "auto" and world > 1)):
         t0 = ph.now()
         t = budget.plan("exact", a.exact_timeout, 5.0)
         exact = _exact_block(a, world, rank, t) if t else {"exact": {}, "exact_detail": _skipped(budget)}
@@ -927,6 +954,8 @@ def main() -> int:
         # spinning on them, go with it - and never this one, which still
         # prints the line.
         fsdp_kw = dict(schedule=a.schedule, wire_dtype="bf16")
+        # the headline's outputs (rank 0 of the child writes them after its timed steps)
+        dump_kw = dict(dump_outputs=os.path.abspath(a.dump_outputs)) if a.dump_outputs else {}
         t0 = ph.now()
         est0 = _Estimator(a, world, 20.0, 0, 3000.0)
         nominal = est0.setup + (a.warmup + a.steps) * est0.iter_s("fsdp", a.model, (a.units, world))
@@ -935,7 +964,7 @@ def main() -> int:
             # (the headline always runs: at least 60 s, more when the budget has it)
             t = budget.plan(tag.lstrip("."), max(60.0, est0.want(nominal, 300)), 1.0) or 60.0
             d = _child_run(a, world, rank, tag, "fsdp", a.model, (a.units, world), t, backend=a.backend,
-                           graph=graph, compute=a.compute, warmup=a.warmup, runs=a.steps, **fsdp_kw)
+                           graph=graph, compute=a.compute, warmup=a.warmup, runs=a.steps, **fsdp_kw, **dump_kw)
             return d if rank == 0 else {}
 
         try:
@@ -984,7 +1013,8 @@ def main() -> int:
             try:
                 d = _child_run(a, world, rank, ".hfb", "fsdp", a.model, (a.units, world), t, backend=fb,
                                graph=use_graph, compute=a.compute, warmup=a.warmup, runs=a.steps,
-                               **dict(schedule=a.schedule, wire_dtype="bf16"))
+                               **dict(schedule=a.schedule, wire_dtype="bf16"),
+                               **(dict(dump_outputs=os.path.abspath(a.dump_outputs)) if a.dump_outputs else {}))
                 doc = d if rank == 0 else {}
                 a.backend = a.hybrid_backend = fb
             except Exception as e:  # noqa: BLE001
@@ -992,7 +1022,7 @@ def main() -> int:
         ph.add("headline_fallback", t0)
     head_ms = doc["global"]["dlnb"]["iteration"]["timed_ms_per_iter"] if doc else 3000.0
     est = _Estimator(a, world, ph.s.get("headline", 30.0), a.warmup + a.steps, head_ms)
-    if doc is not None:
+    if doc is not None and a.full:
         # Secondary measurements, in order of value, each a bounded child run
         # of every rank: failures and overruns are reported, never fatal.
         if a.c5_model != "none":
@@ -1068,7 +1098,8 @@ def main() -> int:
         return 0
     out: Dict[str, Any] = {"metric": METRIC, "value": None, "unit": "ms", "n_gpus": world, "steps": a.steps,
                            "warmup": a.warmup, "ms_per_step": None, "higher_is_better": False, "scaling": "weak",
-                           "vs_baseline": None, "dtype": "bf16"}
+                           "vs_baseline": None, "dtype": "bf16", "full": bool(a.full),
+                           "native_build": native_build}
     if doc is not None:
         g = doc["global"]
         it = g["dlnb"]["iteration"]

@@ -201,6 +201,13 @@ class ComputeEngine {
   // construction and record nothing. Every GPU mode also feeds its tasks'
   // start (and end) stamps to t's stall timers.
   virtual void set_task_timers(TimerSet* t) { (void)t; }
+  // The GEMM modes' product C = A.B^T (device memory, `count` elements of
+  // type t, zeroed before the first task): every tile a task reached holds
+  // its product, whichever task wrote it last. False: the mode computes none.
+  virtual bool product(const void** c, size_t* count, DType* t) const {
+    (void)c; (void)count; (void)t;
+    return false;
+  }
   virtual Json describe() const = 0;
   virtual ComputeMode mode() const = 0;
 };

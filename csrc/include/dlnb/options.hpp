@@ -81,6 +81,9 @@ struct Options {
   // P2P group and compute task of every rank, written by rank 0
   std::string timeline_path;
   int timeline_iters = 2;  // timed iterations kept in it (0 = all)
+  // directory rank 0 writes the last timed iteration's result buffers to
+  // (Strategy::outputs, <name>.npy in float32); empty = off
+  std::string dump_outputs;
   int comm_cus = 32;    // CUs left free by the persistent compute for collectives
   // RCCL maxCTAs per communicator on a comm lane: -1 = comm_cus / lanes
   // (runner.cpp, collective_lanes), 0 = RCCL's default, N = N.

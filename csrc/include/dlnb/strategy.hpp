@@ -71,6 +71,14 @@ std::vector<int> inner_group(int rank, int inner, int stages);  // same (dp, sta
 std::vector<int> pp_group(int rank, int inner, int stages);     // same (dp, inner)
 std::vector<int> dp_group(int rank, int inner, int stages, int world);  // same (stage, inner)
 
+// A result buffer of an iteration (device memory of ctx.dev), by name.
+struct OutputView {
+  std::string name;
+  const void* data;
+  size_t count;
+  DType dtype;
+};
+
 class Strategy {
  public:
   virtual ~Strategy() = default;
@@ -111,6 +119,10 @@ class Strategy {
   // The timer of the iteration's last collective (the runner reports its
   // last entry per timed iteration: iteration_last_collective_ms).
   virtual std::string tail_collective_timer() const { return ""; }
+  // What an iteration leaves for its caller: the buffers the collectives (and
+  // the optimizer) wrote, valid after synchronize() (--dump-outputs). Empty:
+  // the strategy names none.
+  virtual std::vector<OutputView> outputs() const { return {}; }
   TimerSet* timers() { return timers_.get(); }
 
  protected:
@@ -196,6 +208,13 @@ struct CommStat {
   std::string timer;    // timer key holding the op durations
 };
 Json comm_stats_json(const std::vector<CommStat>& stats, const TimerSet& t);
+
+// --dump-outputs: writes every output of the strategy, and the compute
+// engine's GEMM product, to dir/<name>.npy as float32 (dump.cpp). At most
+// 48 MB in all: a larger buffer is written as a fixed sample (blocks of 1024
+// elements, one per equal stretch of the buffer, at offsets drawn from a
+// seeded hash of the name). Call after the device is idle.
+void dump_outputs(Context& ctx, const Strategy& strat, const std::string& dir);
 
 void print_topology(Context& ctx);
 

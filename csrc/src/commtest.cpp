@@ -32,6 +32,8 @@
 #include <thread>
 #include <sstream>
 
+#include <unistd.h>
+
 #include "dlnb/strategy.hpp"
 #include "dlnb/xgmi.hpp"
 
@@ -470,8 +472,14 @@ int run_suite(Context& ctx, const std::vector<std::string>& backends, const std:
   if (ctx.dev->kind() == DeviceKind::GPU) j["runtime"] = runtime_info();
   if (me == 0) std::cout << j.dump() << std::endl;
   if (!json_path.empty()) {
-    std::ofstream f(json_path);
-    f << j.dump(1) << "\n";
+    // (ranks given the same path: each writes its own file and renames it into
+    // place, so the path always holds one whole report, never two interleaved)
+    const std::string tmp = json_path + ".tmp." + std::to_string(static_cast<long>(getpid()));
+    {
+      std::ofstream f(tmp);
+      f << j.dump(1) << "\n";
+    }
+    if (std::rename(tmp.c_str(), json_path.c_str()) != 0) std::remove(tmp.c_str());
   }
   return all_ok ? 0 : 3;
 }

@@ -505,6 +505,13 @@ class GpuCompute : public ComputeEngine {
     return j;
   }
   ComputeMode mode() const override { return mode_; }
+  bool product(const void** c, size_t* count, DType* t) const override {
+    if (!C_.data()) return false;
+    *c = C_.data();
+    *count = static_cast<size_t>(kMmax) * N_;
+    *t = DType::BF16;
+    return true;
+  }
 
  private:
   uint64_t ticks(double us) const { return static_cast<uint64_t>(us * 1e-6 * hz() + 0.5); }
@@ -695,6 +702,8 @@ class GpuCompute : public ComputeEngine {
     auto s = dev_.create_stream(false);
     dev_.fill_random(A_.data(), static_cast<size_t>(Mmax) * K_, dtype_, 1, *s);
     dev_.fill_random(B_.data(), static_cast<size_t>(N_) * K_, dtype_, 2, *s);
+    // (a tile no task reaches reads as 0 in product(), not as whatever the allocation held)
+    dev_.memset_async(C_.data(), 0, C_.bytes(), *s);
     s->synchronize();
   }
 

@@ -110,6 +110,8 @@ std::string usage(StrategyKind kind, const std::string& prog) {
      << "  --trace                emit roctx ranges (rocprofv3 --marker-trace)\n"
      << "  --timeline PATH        device timeline of every rank (Chrome / Perfetto trace JSON, rank 0 writes it)\n"
      << "  --timeline-iters N     timed iterations kept in the timeline (default 2, 0 = all)\n"
+     << "  --dump-outputs DIR     after the timed runs, rank 0 writes what the last iteration left in the\n"
+     << "                         strategy's result buffers to DIR/<name>.npy (float32; a fixed sample of large ones)\n"
      << "  --comm-cus N           CUs the gemm compute leaves free for collectives (default 32)\n"
      << "  --rccl-max-ctas N      RCCL blocks per collective on each comm lane (default: comm-cus / lanes;\n"
      << "                         0 = RCCL's own choice)\n"
@@ -199,6 +201,8 @@ Options parse_options(StrategyKind kind, int argc, const char* const* argv) {
     } else if (is("--timeline-iters")) {
       o.timeline_iters = std::stoi(val("timeline-iters"));
       DLNB_REQUIRE(o.timeline_iters >= 0, "--timeline-iters must be >= 0");
+    } else if (is("--dump-outputs")) {
+      o.dump_outputs = val("dump-outputs");
     } else if (is("--stats-file")) {
       o.stats_file = val("stats-file");
     } else if (is("--store")) {

@@ -1177,6 +1177,7 @@ Json run_rank_impl(const Options& opt, Context& ctx, std::unique_ptr<Strategy>& 
   ctx.dev->synchronize();
   ctx.hg().barrier();
   const double timed_region = ctx.hg().allreduce_max(now_s() - T0);
+  if (!opt.dump_outputs.empty()) dump_outputs(ctx, *strat, opt.dump_outputs);
 
   // ---- report
   Json rank = strat->rank_json();

@@ -31,6 +31,8 @@
 //     ordered by events;
 //   * buffers are exactly sized in the wire dtype: llama3_8b at F=8 needs
 //     2x shards (2 GB) + 4 unit buffers (2 GB) on a 288 GB MI355X.
+#include <cstdio>
+
 #include "dlnb/strategy.hpp"
 
 namespace dlnb {
@@ -316,6 +318,24 @@ class Fsdp : public Strategy {
     for (auto& c : comms_) cs.push_back(c.get());
     sync_streams(ss, cs, *ctx_->dev);
     timers_->resolve();
+  }
+
+  // The step's results: every unit's reduced gradient shard, the two gather
+  // buffers (the parameters of the last two units gathered: units 1 and 0)
+  // and, with --optimizer, the updated parameter shards.
+  std::vector<OutputView> outputs() const override {
+    std::vector<OutputView> v;
+    auto name = [](const char* stem, int i) {
+      char b[48];
+      std::snprintf(b, sizeof b, "%s_%03d", stem, i);
+      return std::string(b);
+    };
+    for (int u = 0; u < U_; ++u) v.push_back({name("grad_shard", u), grads_[u].data(), shard_[u], ctx_->wire});
+    for (int b = 0; b < 2 && b < U_; ++b)  // (one unit: the second buffer is never written)
+      v.push_back({name("gathered_params", b), gathered_[b].data(), shard_[b] * F_, ctx_->wire});
+    if (ctx_->opt.optimizer)
+      for (int u = 0; u < U_; ++u) v.push_back({name("param_shard", u), params_[u].data(), shard_[u], ctx_->wire});
+    return v;
   }
 
   std::string tail_collective_timer() const override { return R_ > 1 ? "allreduce_time" : "reduce_scatter"; }

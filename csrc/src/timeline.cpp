@@ -435,6 +435,7 @@ class TracingCompute : public ComputeEngine {
   void reset_capped(Stream& s) override { in_->reset_capped(s); }
   bool chain_counters(ChainCounters& c) override { return in_->chain_counters(c); }
   void set_task_timers(TimerSet* t) override { in_->set_task_timers(t); }
+  bool product(const void** c, size_t* count, DType* t) const override { return in_->product(c, count, t); }
   Json describe() const override { return in_->describe(); }
   ComputeMode mode() const override { return in_->mode(); }
 

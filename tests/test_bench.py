@@ -34,7 +34,7 @@ def test_bench_torchrun_cpu(n, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(n), "--steps", "2", "--warmup", "1", "--backend", "cpu", "--compute", "sleep",
-           "--link-bench", "on", "--link-sizes", "4096,65536", "--timeline-block", "on"] + TINY
+           "--link-bench", "on", "--link-sizes", "4096,65536", "--timeline-block", "on", "--full"] + TINY
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=str(tmp_path),
                        env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert p.returncode == 0, p.stderr[-3000:]
@@ -99,7 +99,7 @@ def test_bench_hybrid_blocks_eight_ranks_cpu(tmp_path):
     n = 8
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(n), "--steps", "1", "--warmup", "0", "--backend", "cpu", "--compute", "sleep",
+           "--gpus", str(n), "--full", "--steps", "1", "--warmup", "0", "--backend", "cpu", "--compute", "sleep",
            "--hybrids", "on", "--c3-model", "tiny_deep_8_bfloat16", "--c3", "2,4,4",
            "--c4-model", "tiny_moe_8_bfloat16", "--c4", "2,8,4", "--exact", "off", "--c5-model", "none"] + TINY[:6]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=str(tmp_path),
@@ -134,7 +134,7 @@ def test_bench_hybrid_blocks_eight_ranks_cpu(tmp_path):
 def _torchrun(n, args, tmp_path, env=None, timeout=300):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(n)] + args
+           "--gpus", str(n), "--full"] + args
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=str(tmp_path),
                        env=dict(os.environ, OMP_NUM_THREADS="1", **(env or {})))
     assert p.returncode == 0, p.stderr[-3000:]
@@ -245,7 +245,7 @@ def test_bench_two_nodes_cpu(tmp_path):
     for nr in (0, 1):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=2", f"--node-rank={nr}", "--nproc-per-node=2",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-               "--gpus", "4", "--steps", "2", "--warmup", "1", "--backend", "cpu", "--compute", "sleep"] + TINY
+               "--gpus", "4", "--full", "--steps", "2", "--warmup", "1", "--backend", "cpu", "--compute", "sleep"] + TINY
         procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=str(tmp_path), env=dict(os.environ, OMP_NUM_THREADS="1")))
     outs = [p.communicate(timeout=300) for p in procs]
@@ -261,7 +261,7 @@ def test_bench_two_nodes_cpu(tmp_path):
 
 
 def test_bench_single_rank_reports_no_bus_bandwidth(tmp_path):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "0",
                         "--backend", "cpu", "--compute", "sleep"] + TINY,
                        capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
@@ -292,7 +292,7 @@ def test_bench_gpu_single_rank_secondaries(tmp_path):
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"] + TINY,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1"] + TINY,
                        capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)
@@ -333,7 +333,7 @@ def test_bench_gpu_headline_device_fault_still_prints_the_line(tmp_path):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = dict(os.environ, DLNB_INJECT_FAULT="rank=0,iter=0,mode=gate,block=headline", DLNB_TIMEOUT="5")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                         "--no-c5-ctas-ab", "--c5-bucket-ratio", "0", "--stretch-steps", "0"] + TINY,
                        capture_output=True, text=True, timeout=300, cwd=str(tmp_path), env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -356,7 +356,7 @@ def test_bench_torchrun_xgmi_two_ranks_one_gpu(tmp_path):
         pytest.skip("no GPU")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "xgmi", "--devices", "0,0",
+           "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--backend", "xgmi", "--devices", "0,0",
            "--link-sizes", "1048576"] + TINY
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=str(tmp_path),
                        env=dict(os.environ, DLNB_XGMI_TIMEOUT_S="60"))
@@ -395,7 +395,7 @@ def test_bench_headline_fallback_two_ranks_one_gpu(tmp_path):
         pytest.skip("no GPU")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--devices", "0,0", "--link-sizes", "1048576",
+           "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--devices", "0,0", "--link-sizes", "1048576",
            "--wall-budget-s", "240"] + TINY
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=str(tmp_path),
                        env=dict(os.environ, DLNB_XGMI_TIMEOUT_S="60"))
@@ -409,3 +409,109 @@ def test_bench_headline_fallback_two_ranks_one_gpu(tmp_path):
     assert o["config"]["backend"] == "XGMI" and o["verified"] == {"xgmi": True}
     assert o["comm_bound"]["ms_per_step"] > 0 and o["comm_bound"]["backend"] == "XGMI"
     assert o["phase_seconds"]["total"] <= 240
+
+
+SECONDARY_KEYS = {"comm_bound", "compute_stretch", "gemm_work_ms_per_step", "exact", "exact_detail", "link_bench",
+                  "model_fit", "timeline", "comm_bound_xgmi", "headline_xgmi", "hybrid_3d", "hybrid_3d_moe"}
+
+
+def _plain(extra, tmp_path, dump, timeout=120):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", dump] + extra + TINY[:6] + ["--units", "4"],
+                       capture_output=True, text=True, timeout=timeout, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = _json_lines(p.stdout)
+    assert len(lines) == 1, p.stdout
+    return lines[0]
+
+
+def _load_dump(d):
+    np = pytest.importorskip("numpy")
+    out = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert all(f.endswith(".npy") for f in os.listdir(d))
+    assert all(a.dtype == np.float32 and a.ndim == 1 for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    return out
+
+
+def _check_fsdp_dump(a, b):
+    """Two dumps of the tiny 4-unit FSDP step at 1 rank: the same files with the same content; a 1-rank
+    reduce-scatter copies the full-gradient buffer of its unit's parity, so units 0 and 2 (and 1 and 3, one
+    element shorter) leave the same shard; the values are the fills' bf16 in [-1, 1]."""
+    np = pytest.importorskip("numpy")
+    names = ["gathered_params_000", "gathered_params_001"] + [f"grad_shard_{u:03d}" for u in range(4)]
+    assert [k for k in a if k != "gemm_product"] == names and list(a) == list(b)
+    for k in names:
+        assert np.array_equal(a[k], b[k]), k
+        assert np.abs(a[k]).max() <= 1.0 and a[k].std() > 0.3, k
+    # Model_Size 1000003 over 4 units: shards of 250001, 250001, 250001, 250000 elements
+    assert [a[f"grad_shard_{u:03d}"].size for u in range(4)] == [250001, 250001, 250001, 250000]
+    assert np.array_equal(a["grad_shard_000"], a["grad_shard_002"])
+    assert np.array_equal(a["grad_shard_001"][:250000], a["grad_shard_003"])
+    assert not np.array_equal(a["grad_shard_000"], a["grad_shard_001"])
+    assert a["gathered_params_000"].size == 250001 and not np.array_equal(a["gathered_params_000"], a["grad_shard_000"])
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs_cpu(tmp_path):
+    """Without --full the bench times the headline and nothing else (no secondary block, no exactness pass:
+    one phase), --steps sets the number of timed steps, and --dump-outputs writes the last step's result
+    buffers as float32 .npy files, the same from run to run."""
+    o = _plain(["--backend", "cpu", "--compute", "sleep"], tmp_path, "d1")
+    assert o["full"] is False and not SECONDARY_KEYS & set(o), sorted(SECONDARY_KEYS & set(o))
+    assert o["steps"] == 3 and len(o["per_run_ms"]) == 3 and o["ms_per_step"] == o["value"] > 0
+    assert o["unit"] == "ms" and o["higher_is_better"] is False and o["dtype"] == "bf16"
+    assert set(o["phase_seconds"]) == {"headline", "total"} and o["verified"] is None
+    assert o["native_build"].startswith("dlnetbench_amd") and "gfx950" in o["native_build"]
+    _plain(["--backend", "cpu", "--compute", "sleep"], tmp_path, os.path.join(str(tmp_path), "sub", "d2"))
+    _check_fsdp_dump(_load_dump(os.path.join(str(tmp_path), "d1")), _load_dump(os.path.join(str(tmp_path), "sub", "d2")))
+
+
+def test_dump_outputs_samples_large_buffers_cpu(tmp_path):
+    """A buffer over its share of the 48 MB is written as a sample of 1024-element blocks, one per equal
+    stretch of the buffer at an offset fixed by the buffer's name: 2 outputs of 7 M elements -> 6 Mi each,
+    the same elements in two runs, the two buffers sampled at different offsets."""
+    np = pytest.importorskip("numpy")
+    sys.path.insert(0, ROOT)
+    from dlnetbench_amd import engine
+    with open(os.path.join(DATA, "model_stats", "tiny_dense_8_bfloat16.txt")) as f:
+        text = f.read()
+    n_big, share = 7000003, 6 << 20
+    dumps = []
+    for tag, size in (("a", n_big), ("b", n_big)):
+        stats = tmp_path / f"{tag}.txt"
+        stats.write_text(text.replace("Model_Size:1000003", f"Model_Size:{size}"))
+        d = str(tmp_path / tag)
+        engine.run_native("fsdp", "tiny_dense_8_bfloat16", 1, 1, base_path=DATA, backend="cpu", compute="sleep",
+                          warmup=0, runs=1, stats_file=str(stats), dump_outputs=d, timeout=60)
+        dumps.append(_load_dump(d))
+    a, b = dumps
+    assert list(a) == ["gathered_params_000", "grad_shard_000"]
+    for k in a:
+        assert a[k].size == share and np.array_equal(a[k], b[k]), k
+        assert np.abs(a[k]).max() <= 1.0 and a[k].std() > 0.3, k
+    # the two buffers are sampled at different offsets
+    assert not np.array_equal(a["gathered_params_000"], a["grad_shard_000"])
+
+
+@pytest.mark.gpu
+def test_bench_gpu_plain_run_dumps_outputs(tmp_path):
+    """The plain run on the GPU (RCCL, HIP graph, MFMA GEMM compute) with --dump-outputs, twice: no secondary
+    block, the collectives' result buffers identical from run to run, and the GEMM product C = A.B^T of the
+    compute tasks equal wherever both runs' tasks reached a tile (a 0.5-ms task of the tiny model need not
+    reach every tile; unreached tiles read 0)."""
+    torch = pytest.importorskip("torch")
+    np = pytest.importorskip("numpy")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    o = _plain([], tmp_path, "g1", timeout=200)
+    assert o["full"] is False and not SECONDARY_KEYS & set(o), sorted(SECONDARY_KEYS & set(o))
+    assert o["config"]["backend"] == "RCCL" and o["config"]["hip_graph"] is True
+    assert o["steps"] == 3 and len(o["per_run_ms"]) == 3 and o["ms_per_step"] == o["value"] > 0
+    _plain([], tmp_path, "g2", timeout=200)
+    a, b = _load_dump(os.path.join(str(tmp_path), "g1")), _load_dump(os.path.join(str(tmp_path), "g2"))
+    _check_fsdp_dump(a, b)
+    ca, cb = a["gemm_product"], b["gemm_product"]
+    # C is 8192 x 1024 (N at least 1024): over its share of 12 Mi / 7 outputs, so a sample of whole blocks
+    assert ca.size == cb.size == (12 << 20) // 7 // 1024 * 1024 and np.isfinite(ca).all() and np.isfinite(cb).all()
+    both = (ca != 0) & (cb != 0)
+    assert both.mean() > 0.01 and np.array_equal(ca[both], cb[both])
