@@ -709,12 +709,9 @@ void gemm_tn_8phase(const void* A, const void* B, void* C, int M, int N, int K, 
   if (e != hipSuccess) DLNB_THROW("gemm 8-phase launch failed: " << hipGetErrorString(e));
 }
 
-// Tile-order group of the per-tile deadline kernels (8; DLNB_DEADLINE_GROUP, A/B knob read per launch).
-static int deadline_group() {
-  const char* env = std::getenv("DLNB_DEADLINE_GROUP");
-  const int g = env ? std::atoi(env) : 0;
-  return g > 0 ? g : 8;
-}
+// Tile-order group of the per-tile deadline kernels (groups of 4 and 8 did the
+// same MFMA work per clock: profiles/gemm_group_r4.md, headline_prof_r6.md).
+static constexpr int deadline_group() { return 8; }
 
 // The per-tile 8-phase deadline kernel in program mode (bf16, or fp8 K-tiles
 // the 4-wave kernel does not take).

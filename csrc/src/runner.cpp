@@ -1,5 +1,6 @@
 // Benchmark runner shared by all strategies: bootstrap, device/backend
-// selection, warm-up, run-count estimation, timed runs, loop mode, report.
+// selection, warm-up, run-count estimation, timed runs, loop mode. The
+// iteration's graph replay is replay.cpp, the report document report.cpp.
 //
 // Reference flow: main() of each driver (e.g. cpp/data_parallel/dp.cpp:127-303):
 // parse args -> read stats -> MPI_Init -> topology print -> set device ->
@@ -25,12 +26,8 @@
 
 #include <sys/prctl.h>
 
-extern char** environ;
-
-#include "dlnb/aux.hpp"
 #include "dlnb/kernels.hpp"
-#include "dlnb/strategy.hpp"
-#include "dlnb/xgmi.hpp"
+#include "dlnb/report.hpp"
 
 namespace dlnb {
 
@@ -170,21 +167,6 @@ void optimizer_step(Context& ctx, Stream& s, void* param, void* mom, const void*
     kernels::sgd_momentum_bf16(param, mom, grad, n, 1e-4f, 0.9f, s.native(), end_stamp, done);
     return;
   }
-  if (end_stamp) {
-    // (the CPU device's stamp: when the stream reaches it, i.e. after the task below)
-    ctx.dev->host_task(s, [param, mom, grad, n] {
-      auto* p = static_cast<uint16_t*>(param);
-      auto* m = static_cast<uint16_t*>(mom);
-      auto* g = static_cast<const uint16_t*>(grad);
-      for (size_t i = 0; i < n; ++i) {
-        float mv = 0.9f * bf16_to_float(m[i]) + bf16_to_float(g[i]);
-        m[i] = float_to_bf16(mv);
-        p[i] = float_to_bf16(bf16_to_float(p[i]) - 1e-4f * mv);
-      }
-    });
-    ctx.dev->stamp(s, end_stamp);
-    return;
-  }
   ctx.dev->host_task(s, [param, mom, grad, n] {
     auto* p = static_cast<uint16_t*>(param);
     auto* m = static_cast<uint16_t*>(mom);
@@ -195,6 +177,8 @@ void optimizer_step(Context& ctx, Stream& s, void* param, void* mom, const void*
       p[i] = float_to_bf16(bf16_to_float(p[i]) - 1e-4f * mv);
     }
   });
+  // (the CPU device's stamp: when the stream reaches it, i.e. after the task above)
+  if (end_stamp) ctx.dev->stamp(s, end_stamp);
 }
 
 // ------------------------------------------------------------- topology
@@ -250,14 +234,6 @@ std::vector<int> parse_device_list(const std::string& s) {
     if (!t.empty()) v.push_back(std::stoi(t));
   }
   return v;
-}
-
-double percentile(std::vector<double> v, double q) {
-  if (v.empty()) return 0;
-  std::sort(v.begin(), v.end());
-  double pos = q * (v.size() - 1);
-  size_t lo = static_cast<size_t>(std::floor(pos)), hi = static_cast<size_t>(std::ceil(pos));
-  return v[lo] + (v[hi] - v[lo]) * (pos - lo);
 }
 
 std::unique_ptr<Strategy> make_strategy(StrategyKind k) {
@@ -581,7 +557,9 @@ Json run_rank(const Options& opt, std::unique_ptr<Bootstrap> boot) {
   }
 }
 
-Json run_rank_impl(const Options& opt, Context& ctx, std::unique_ptr<Strategy>& strat) {
+// Backend / device, workload, compute engine, the CTA budget, strategy setup
+// and timers: everything before the first iteration.
+RunSetup setup_rank(const Options& opt, Context& ctx, std::unique_ptr<Strategy>& strat) {
   const RankInfo& ri = ctx.boot->info;
 
   // ---- backend / device (cpp/utils.hpp:62-117 set_local_device)
@@ -628,25 +606,27 @@ Json run_rank_impl(const Options& opt, Context& ctx, std::unique_ptr<Strategy>& 
   Tracer::get().enable(opt.trace);
   std::unique_ptr<EnergyMeter> meter =
       ctx.dev->kind() == DeviceKind::GPU ? EnergyMeter::open_gpu(ctx.dev->index()) : EnergyMeter::none();
-  FaultInjector fault(ri.rank);
-  long long iter_no = 0;
+  RunSetup su(ri.rank);
+  su.meter = std::move(meter);
+  su.backend = backend;
+  su.stats_path = stats_path;
 
   // ---- RCCL CTA budget: every comm lane's collective kernel must find CUs
   // beside the persistent compute (which leaves comm_cus CUs free), so
   // lanes x maxCTAs <= comm_cus; else blocks of one communicator's kernel can
   // sit in the queue while another communicator's kernel holds the free CUs
   // spinning on a peer that waits for them.
-  const int lanes = collective_lanes(opt, ri.world_size);
+  const int lanes = su.lanes = collective_lanes(opt, ri.world_size);
   // xgmi kernels are budgeted too: a lane's kernel gets 4 blocks (512
   // threads, no LDS) per budgeted CU (comm_xgmi.cpp).
-  const bool rccl = backend == "rccl" || backend == "mixed" || backend == "xgmi";
-  const bool gemm_compute = ctx.compute->mode() == ComputeMode::Gemm;
-  if (rccl) {
+  su.rccl = backend == "rccl" || backend == "mixed" || backend == "xgmi";
+  su.gemm_compute = ctx.compute->mode() == ComputeMode::Gemm;
+  if (su.rccl) {
     if (opt.rccl_max_ctas >= 0)
       ctx.lane_ctas = opt.rccl_max_ctas;
     else
-      ctx.lane_ctas = gemm_compute ? std::max(1, opt.comm_cus / lanes) : 0;
-    if (ctx.lane_ctas > 0 && gemm_compute && lanes * ctx.lane_ctas > opt.comm_cus && ri.rank == 0)
+      ctx.lane_ctas = su.gemm_compute ? std::max(1, opt.comm_cus / lanes) : 0;
+    if (ctx.lane_ctas > 0 && su.gemm_compute && lanes * ctx.lane_ctas > opt.comm_cus && ri.rank == 0)
       std::cerr << "[dlnb] warning: " << lanes << " comm lanes x " << ctx.lane_ctas << " RCCL CTAs > --comm-cus "
                 << opt.comm_cus << ": concurrent collectives may not all fit beside the compute" << std::endl;
   }
@@ -668,332 +648,34 @@ Json run_rank_impl(const Options& opt, Context& ctx, std::unique_ptr<Strategy>& 
       std::cerr << "[dlnb] warning: " << strat->streams().size() << " streams per rank > GPU_MAX_HW_QUEUES=" << nq
                 << "; streams will share hardware queues" << std::endl;
   }
-  // DLNB_INJECT_FAULT mode=task: a task that throws on the first stream
-  // (CPU devices; library hosts must get the error back, not lose the process)
-  auto inject_task = [&] {
-    DLNB_REQUIRE(ctx.dev->kind() == DeviceKind::CPU, "DLNB_INJECT_FAULT mode=task needs a CPU device");
-    ctx.dev->host_task(*strat->streams()[0], [] { DLNB_THROW("injected fault in a stream task"); });
-  };
   // the deadline clock's measured rate (kernels::wallclock_hz): taken here,
   // after setup gave its window time, and never inside a graph capture
   if (ctx.dev->kind() == DeviceKind::GPU) (void)ctx.dev->stamp_hz();
+  if (ctx.timeline) ctx.timeline->calibrate(*strat->streams()[0]);
+  su.rkey = strat->runtime_key();
+  strat->timers()->ensure(su.rkey);
+  ctx.compute->set_task_timers(strat->timers());
+  return su;
+}
+
+// Start of every iteration, warm-up and timed (the fault injector counts them).
+void next_iteration(RunSetup& su, Context& ctx, Strategy& strat) {
+  // DLNB_INJECT_FAULT mode=task: a task that throws on the first stream
+  // (CPU devices; library hosts must get the error back, not lose the process)
+  su.fault.at_iteration(su.iter_no++, [&ctx, &strat] {
+    DLNB_REQUIRE(ctx.dev->kind() == DeviceKind::CPU, "DLNB_INJECT_FAULT mode=task needs a CPU device");
+    ctx.dev->host_task(*strat.streams()[0], [] { DLNB_THROW("injected fault in a stream task"); });
+  });
+}
+
+void warm_up(Context& ctx, Strategy& strat, RunSetup& su, Replay& replay, std::vector<double>& warm) {
   Timeline* TL = ctx.timeline.get();
-  if (TL) TL->calibrate(*strat->streams()[0]);
-  TimerSet& T = *strat->timers();
-  const char* rkey = strat->runtime_key();
-  T.ensure(rkey);
-  ctx.compute->set_task_timers(&T);
-
-  // ---- HIP graph: capture one iteration, replay it every iteration.
-  // Lane graphs (the default): every stream of the strategy is captured into
-  // its own linear graph, launched on that stream, and the streams' ordering
-  // is carried by device gates (Device::set_gate_events: an event record
-  // raises a gate, a wait spins on it) instead of graph edges. The graph
-  // executor then has no fork to spread over its hardware queues: compute
-  // stays on the compute stream's queue and every collective on its lane's,
-  // so no compute task queues behind a collective (profiles/absorb_r4.md), and
-  // every stamp pair on one stream times exactly that stream's work. It needs
-  // every stream on a hardware queue of its own (a gate wait would otherwise
-  // hold the queue its signal sits behind): probed first, and a single graph
-  // with event edges when they share one (lane_graphs.reason says why).
-  std::unique_ptr<GraphExec> graph;
-  std::vector<std::unique_ptr<GraphExec>> lane_graphs;
-  // lane graphs: each lane's last node stores the iteration number here (the
-  // host's completion words; Device::lane_done)
-  uint64_t* lane_done = nullptr;
-  size_t lane_done_n = 0;
-  bool joined = false;  // the compute program's join signals the iteration (lane_done[0] alone)
-  struct LaneDone {
-    Device& d;
-    uint64_t*& p;
-    size_t& n;
-    ~LaneDone() {
-      if (p && std::uncaught_exceptions() == 0) d.free_stamps(p, n);
-    }
-  } lane_done_guard{*ctx.dev, lane_done, lane_done_n};
-  Json lane_info = Json::object();
-  std::vector<Stream*> lanes_ss;  // streams the replay is launched on (lane graphs: each; else the compute stream)
-  std::vector<std::unique_ptr<Stream>> alt_owned;
-  std::vector<Stream*> alt_ss;    // lane graphs: the second set, odd replays
-  std::vector<Stream*> ss, others;  // --graph: the strategy's streams (compute first)
-  // Capture one iteration: lane graphs when `lanes` (the capture may still
-  // fall back to the single graph: not linear, no program), else the single
-  // graph; `why` is the reason reported when there are no lanes.
-  std::function<void(bool, std::string)> build_graph = [&](bool lanes, std::string why) {
-    TraceRange tr("dlnb:graph_capture");
-    T.begin_capture();
-    if (TL) TL->begin_capture();
-    if (lanes) {
-      ctx.dev->set_gate_events(true);
-      // each lane ends by clearing its own deadline slot for the next replay
-      lane_done_n = ss.size();
-      lane_done = ctx.dev->alloc_stamps(lane_done_n);
-      // A compute program on the compute lane ends with a join on the other
-      // lanes' end gates and signals the whole iteration from inside the
-      // kernel (ComputeEngine::set_lane_join); otherwise every lane ends with
-      // its own done word (and clears its deadline slot).
-      std::vector<uint64_t*> end_gates;
-      for (size_t i = 1; i < ss.size(); ++i) end_gates.push_back(ctx.dev->alloc_gate());
-      ctx.compute->set_lane_join(*ss[0], end_gates, 1u, lane_done);
-      const long progs0 = ctx.compute->programs_on(*ss[0]);
-      lane_graphs = ctx.dev->capture_lanes(
-          ss, [&] {
-            T.iteration_start(*ss[0]);
-            strat->enqueue_iteration();
-            T.finish_stalls();
-          },
-          [&](size_t i) {
-            if (ctx.compute->program_joined(*ss[0])) {
-              if (i > 0) ctx.dev->signal_gate(*ss[i], end_gates[i - 1], 1u);
-            } else {
-              ctx.compute->reset_slot(*ss[i]);
-              ctx.dev->lane_done(*ss[i], lane_done + i);
-            }
-            // The graph's last kernel carries its system-scope release (an L2
-            // write-back: ~50 us after a collective's copy, round 5 traces):
-            // a trailing no-op takes it, after the lane's signal is out.
-            if (env_int("DLNB_LANE_TAIL_PAD", 1) != 0) ctx.dev->pad(*ss[i]);
-          });
-      ctx.compute->after_capture();  // the compute programs' task lists
-      joined = ctx.compute->program_joined(*ss[0]);
-      // A lane whose graph is not a chain (a library adding its own stream
-      // to the capture, e.g. a collective's side work joined back) would be
-      // spread over executor streams that may share the compute lane's
-      // hardware queue - where a gate wait could hold the node that raises
-      // its gate. Then the whole iteration is captured as one graph instead.
-      // Lanes pay only when the compute lane is one compute program: a lane
-      // of one launch per task puts every kernel boundary (28-60 us: drain,
-      // dispatch) on one queue, which the single graph spreads over four
-      // (C5 7.40-7.65 ms against 7.27, gemm-work C5 14.5 ms against 7.8:
-      // profiles/lanes_r5.md). DLNB_LANE_GRAPHS=2 keeps such lanes anyway.
-      bool linear = true;
-      for (const auto& g : lane_graphs) linear = linear && g->linear();
-      // ... or when its tasks are long single kernels (the pipeline hybrids:
-      // one task per micro-batch; their boundaries cost little, while the
-      // single graph's executor queues them behind collectives - hybrid_3d
-      // S=2 mb=4 on 2 ranks: 100.0 ms with lanes against 104.9-106.7,
-      // profiles/lanes_n2_r5.md). DLNB_LANE_MIN_TASK_US (1000).
-      const double task_us = ctx.compute->lane_task_us(*ss[0]);
-      const bool long_tasks = task_us >= static_cast<double>(env_int("DLNB_LANE_MIN_TASK_US", 1000)) &&
-                              strat->lanes_without_program();
-      // a compute program per iteration qualifies joined or not (not joined:
-      // work follows it on the compute lane, which then ends with its own
-      // done word - ADVICE r5)
-      // - ONE program launch in the iteration: a task too short for a program
-      // (< 20 us) splits it into several launches with kernels between, whose
-      // boundaries all land on the compute lane's one queue
-      const long progs = ctx.compute->programs_on(*ss[0]) - progs0;
-      const bool program_ok = joined || (progs == 1 && !ctx.compute->program_split(*ss[0])) || long_tasks ||
-                              env_int("DLNB_LANE_GRAPHS", 1) >= 2;
-      lane_info["compute_programs"] = static_cast<double>(progs);
-      lane_info["compute_task_us"] = task_us;
-      const double verdict = ctx.hg().allreduce_max(!linear ? 2.0 : (!program_ok ? 1.0 : 0.0));
-      linear = verdict < 0.5;
-      if (linear) {
-        lanes_ss = ss;
-        // the first replay starts from cleared slots too
-        ctx.compute->reset_clocks(*ss[0]);
-        ss[0]->synchronize();
-        // Every other replay goes to a second set of streams (same
-        // priorities: the compute lane normal, the comm lanes high): a
-        // launched graph's completion holds its queue for ~70-100 us after
-        // its last node (round 5 traces), and the pre-armed next replay would
-        // wait behind it. A graph runs on any stream; its nodes do not depend
-        // on the one it was captured on.
-        // Both sets are streams made here, after setup: replays on the
-        // strategy's own streams (made before the communicators) ran their
-        // collectives slower - every other iteration 0.13 ms (C5) / 0.3 ms
-        // (headline) longer in round 5's A/B - so by default (DLNB_LANE_FRESH)
-        // neither set is the capture's.
-        // (not with ranks sharing the device, DLNB_LANE_SHARED: two processes'
-        // extra stream sets oversubscribe the hardware queues - 2 ranks on one
-        // GPU ran 143.4 ms without and 149.5-164.7 with, profiles/lanes_n2_r5.md)
-        bool alt = env_int("DLNB_LANE_ALTERNATE", ctx.ranks_on_device > 1 ? 0 : 1) != 0;
-        const bool fresh = env_int("DLNB_LANE_FRESH", 1) != 0;
-        if (alt) {
-          std::vector<Stream*> all = fresh ? std::vector<Stream*>() : ss;
-          for (size_t k = 0; k < (fresh ? 2u : 1u); ++k)
-            for (size_t i = 0; i < ss.size(); ++i) {
-              alt_owned.push_back(ctx.dev->create_stream(i > 0));
-              all.push_back(alt_owned.back().get());
-            }
-          std::string detail;
-          alt = ctx.dev->queues_independent(all, 0.05, &detail);
-        }
-        alt = ctx.hg().allreduce_max(alt ? 0.0 : 1.0) < 0.5;
-        if (alt) {
-          const size_t n = ss.size();
-          if (fresh) {
-            lanes_ss.clear();
-            for (size_t i = 0; i < n; ++i) lanes_ss.push_back(alt_owned[i].get());
-          }
-          for (size_t i = 0; i < n; ++i) alt_ss.push_back(alt_owned[(fresh ? n : 0) + i].get());
-        } else {
-          alt_owned.clear();
-        }
-      } else {
-        // the rejected lanes' shapes (which library added what to a capture)
-        Json rej = Json::array();
-        for (const auto& g : lane_graphs) {
-          Json e = Json::object();
-          e["nodes"] = static_cast<double>(g->nodes());
-          e["edges"] = static_cast<double>(g->edges());
-          e["node_types"] = g->node_types();
-          rej.push_back(e);
-        }
-        lane_info["rejected_lane_graphs"] = rej;
-        lane_graphs.clear();
-        ctx.dev->free_stamps(lane_done, lane_done_n);  // the single graph signals after its launch
-        lane_done = nullptr;
-        lane_done_n = 0;
-        joined = false;
-        ctx.dev->set_gate_events(false);
-        lanes = false;
-        why = verdict > 1.5 ? "a lane graph is not linear"
-                            : "the compute lane is not one compute program (and the strategy's launch-per-task "
-                              "lanes do not pay: Strategy::lanes_without_program)";
-        T.end_capture();
-        if (TL) TL->end_capture();
-        T.begin_capture();
-        if (TL) TL->begin_capture();
-      }
-    }
-    if (!lanes) {
-      // the engine's slot reset heads the graph, before every stream's first node
-      graph = ctx.dev->capture(
-          *ss[0], others, [&] {
-            strat->enqueue_iteration();
-            T.finish_stalls();
-          }, [&] {
-            ctx.compute->reset_clocks(*ss[0]);
-            T.iteration_start(*ss[0]);
-          });
-      ctx.compute->after_capture();  // task lists of the launches captured (fixed-work tasks)
-      lanes_ss = {ss[0]};
-    }
-    T.end_capture();
-    if (TL) TL->end_capture();
-    lane_info["enabled"] = lanes;
-    if (lanes) {
-      lane_info["program_join"] = joined;
-      lane_info["alternating_streams"] = !alt_ss.empty();
-    }
-    if (!lanes) lane_info["reason"] = why;
-    Json per = Json::array();
-    size_t total = 0;
-    bool all_linear = true;
-    auto describe = [&](const GraphExec& g) {
-      Json e = Json::object();
-      e["nodes"] = static_cast<double>(g.nodes());
-      e["edges"] = static_cast<double>(g.edges());
-      e["linear"] = g.linear();
-      e["node_types"] = g.node_types();
-      total += g.nodes();
-      all_linear = all_linear && g.linear();
-      per.push_back(e);
-    };
-    if (lanes)
-      for (auto& g : lane_graphs) describe(*g);
-    else
-      describe(*graph);
-    lane_info["graphs"] = per;
-    lane_info["linear"] = all_linear;
-    if (ri.rank == 0 && !opt.quiet) {
-      if (lanes)
-        std::cout << "[dlnb] captured one iteration into " << lane_graphs.size() << " lane graphs of " << total
-                  << " nodes (" << (all_linear ? "all linear" : "NOT all linear") << ")" << std::endl;
-      else
-        std::cout << "[dlnb] captured one iteration into a HIP graph of " << total << " nodes"
-                  << (why.empty() ? "" : " (no lane graphs: " + why + ")") << std::endl;
-    }
-    };
-  if (opt.graph) {
-    DLNB_REQUIRE(ctx.dev->kind() == DeviceKind::GPU, "--graph needs a GPU");
-    // xgmi kernels take their epochs from device-side counters, so a replayed
-    // graph issues fresh ones; the loopback backends synchronise on the host.
-    DLNB_REQUIRE(backend == "rccl" || backend == "xgmi" || backend == "mixed",
-                 "--graph needs --backend rccl, xgmi or mixed");
-    DLNB_REQUIRE(strat->capturable(), "--graph cannot capture --schedule reference (it blocks the host)");
-    ss = strat->streams();
-    others.assign(ss.begin() + 1, ss.end());
-    std::string why;
-    if (env_int("DLNB_LANE_GRAPHS", 1) == 0) {
-      why = "DLNB_LANE_GRAPHS=0";
-    } else if (ss.size() < 2) {
-      why = "one stream";
-    } else if (ctx.ranks_on_device > 1 && env_int("DLNB_LANE_SHARED", 0) == 0) {
-      // a task spinning on its gate holds its CUs, which another rank's
-      // compute on the same device - the one the collective waits for - needs
-      // (DLNB_LANE_SHARED=1, with grids that fit side by side - --comm-cus -
-      // and no slicing: the multi-rank lane path rehearsed on one GPU)
-      why = "ranks share the device";
-    } else {
-      std::string detail;
-      if (!ctx.dev->queues_independent(ss, 0.05, &detail)) why = "streams share a hardware queue (" + detail + ")";
-    }
-    // every rank takes the same decision, and every rank takes part in it
-    bool lanes = ctx.hg().allreduce_max(why.empty() ? 0.0 : 1.0) < 0.5;
-    if (!lanes && why.empty()) why = "another rank cannot use lane graphs";
-    // Gate waits bounded by 4x the compute floor (at least 15 s) unless
-    // DLNB_GATE_TIMEOUT_S is set: a gate that never comes costs the warm-up
-    // that much before the safety valve below, not 60 s per wait.
-    if (!std::getenv("DLNB_GATE_TIMEOUT_S")) {
-      const double t = std::max(15.0, 4.0 * strat->compute_floor_us(ctx) * 1e-6 * opt.time_scale);
-      ctx.dev->set_gate_timeout(t);
-      ctx.compute->set_gate_timeout(t);
-      lane_info["gate_timeout_s"] = t;
-    }
-    build_graph(lanes, why);
-  }
-  const bool replay = graph || !lane_graphs.empty();
-  Stream* origin = replay ? strat->streams()[0] : nullptr;
-  // Device iteration word (gates' sequence numbers): one value per replay,
-  // stored at the head of every lane before its graph runs.
-  uint64_t dev_iter = 0;
-  // the streams replay `it` runs on (lane graphs alternate between two sets)
-  auto lanes_for = [&](uint64_t it) -> const std::vector<Stream*>& {
-    return !alt_ss.empty() && (it & 1) ? alt_ss : lanes_ss;
-  };
-  auto launch_graphs = [&](uint64_t it) {
-    if (lane_graphs.empty()) {
-      graph->launch(*origin);
-      return;
-    }
-    const auto& L = lanes_for(it);
-    for (size_t i = 0; i < lane_graphs.size(); ++i) lane_graphs[i]->launch(*L[i]);
-  };
-  auto enqueue = [&] {
-    if (replay) {
-      const uint64_t it = ++dev_iter;
-      for (Stream* l : lanes_for(it)) ctx.dev->set_iteration(*l, it);
-      launch_graphs(it);
-    } else {
-      T.iteration_start(*strat->streams()[0]);
-      strat->enqueue_iteration();
-      T.finish_stalls();
-    }
-  };
-  // Host wait for the iteration just enqueued: lane graphs by their done words
-  // (the graphs' own completion comes later: each ends with a marker), else
-  // the streams.
-  auto wait_iteration = [&] {
-    if (lane_done) {
-      CompletionFlag cf(lane_done, joined ? 1 : lane_done_n, dev_iter);
-      strat->synchronize();
-    } else {
-      strat->synchronize();
-    }
-  };
-  ctx.hg().barrier();
-
-  // ---- warm-up
-  std::vector<double> warm;
-  for (int i = 0; i < opt.warmup; ++i) {
-    fault.at_iteration(iter_no++, inject_task);
+  for (int i = 0; i < ctx.opt.warmup; ++i) {
+    next_iteration(su, ctx, strat);
     TraceRange tr("dlnb:warmup_iteration");
     double t0 = now_s();
-    enqueue();
-    wait_iteration();
+    replay.enqueue();
+    replay.wait_iteration();
     warm.push_back(now_s() - t0);
     if (TL) TL->collect(-1);
   }
@@ -1001,168 +683,89 @@ Json run_rank_impl(const Options& opt, Context& ctx, std::unique_ptr<Strategy>& 
   // compute floor, in the warm-up: re-capture the single graph and warm it
   // once (every rank alike). A safety valve for a first run on hardware the
   // lanes were not measured on (the 8-GPU node); `lane_graphs.fallback`.
-  if (!lane_graphs.empty() && !warm.empty()) {
-    ComputeEngine::ChainCounters cc;
-    double timeouts = static_cast<double>(ctx.dev->gate_event_timeouts());
-    if (ctx.compute->chain_counters(cc)) timeouts += cc.wait_timeouts + cc.gate_timeouts;
-    const double floor_s = strat->compute_floor_us(ctx) * 1e-6 * opt.time_scale;
-    const bool slow = warm.back() > 2.0 * floor_s + static_cast<double>(env_int("DLNB_LANE_WARM_SLACK_S", 5));
-    if (ctx.hg().allreduce_max((timeouts > 0 || slow) ? 1.0 : 0.0) > 0.5) {
-      const std::string what = timeouts > 0 ? "gate waits timed out in the warm-up"
-                                            : "a warm-up replay ran over twice the compute floor";
-      if (ri.rank == 0 && !opt.quiet) std::cerr << "[dlnb] lane graphs: " << what << "; the single graph instead\n";
-      ctx.dev->synchronize();
-      lane_graphs.clear();
-      if (lane_done) ctx.dev->free_stamps(lane_done, lane_done_n);
-      lane_done = nullptr;
-      lane_done_n = 0;
-      joined = false;
-      alt_ss.clear();
-      alt_owned.clear();
-      ctx.dev->set_gate_events(false);
-      lane_info = Json::object();
-      build_graph(false, "lanes fell back after the warm-up");
-      lane_info["fallback"] = what;
-      fault.at_iteration(iter_no++, inject_task);
-      enqueue();
-      wait_iteration();
+  if (replay.lanes() && !warm.empty()) {
+    const std::string what = replay.warmup_trouble(warm.back());
+    if (!what.empty()) {
+      replay.fall_back_to_single_graph(what);
+      next_iteration(su, ctx, strat);
+      replay.enqueue();
+      replay.wait_iteration();
     }
   }
-  T.clear();
+  strat.timers()->clear();
+}
 
-  int runs = opt.runs;
-  if (opt.min_exectime > 0) {
-    // Skip the first two warm-ups when there are more (cpp/utils.hpp:121-135).
-    double s = 0;
-    int n = 0;
-    for (size_t i = warm.size() > 2 ? 2 : 0; i < warm.size(); ++i, ++n) s += warm[i];
-    double avg = n ? s / n : 1.0;
-    avg = ctx.hg().allreduce_max(avg);
-    runs = std::max(1, static_cast<int>(std::ceil(opt.min_exectime / std::max(avg, 1e-9))));
-    if (ri.rank == 0 && !opt.quiet)
-      std::cout << "Estimated runs based on warm-up times to meet minimum execution time: " << runs << std::endl;
+// --min-exectime: the run count from the warm-up times (every rank takes part).
+int estimate_runs(Context& ctx, const std::vector<double>& warm) {
+  // Skip the first two warm-ups when there are more (cpp/utils.hpp:121-135).
+  double s = 0;
+  int n = 0;
+  for (size_t i = warm.size() > 2 ? 2 : 0; i < warm.size(); ++i, ++n) s += warm[i];
+  double avg = n ? s / n : 1.0;
+  avg = ctx.hg().allreduce_max(avg);
+  const int runs = std::max(1, static_cast<int>(std::ceil(ctx.opt.min_exectime / std::max(avg, 1e-9))));
+  if (ctx.rank() == 0 && !ctx.opt.quiet)
+    std::cout << "Estimated runs based on warm-up times to meet minimum execution time: " << runs << std::endl;
+  return runs;
+}
+
+// Interference generator (the reference's *_loop builds): no timers,
+// runs forever unless --max-loop-iters bounds it.
+Json loop_mode(Context& ctx, Strategy& strat, RunSetup& su, Replay& replay) {
+  const Options& opt = ctx.opt;
+  Timeline* TL = ctx.timeline.get();
+  strat.timers()->set_enabled(false);
+  for (long long it = 0; opt.max_loop_iters == 0 || it < opt.max_loop_iters; ++it) {
+    next_iteration(su, ctx, strat);
+    TraceRange tr("dlnb:loop_iteration");
+    replay.enqueue();
+    replay.wait_iteration();
+    if (TL) TL->collect(-1);
   }
-
-  Json doc = Json::object();
-  if (opt.loop) {
-    // Interference generator (the reference's *_loop builds): no timers,
-    // runs forever unless --max-loop-iters bounds it.
-    T.set_enabled(false);
-    for (long long it = 0; opt.max_loop_iters == 0 || it < opt.max_loop_iters; ++it) {
-      fault.at_iteration(iter_no++, inject_task);
-      TraceRange tr("dlnb:loop_iteration");
-      enqueue();
-      wait_iteration();
-      if (TL) TL->collect(-1);
-    }
-    ctx.hg().barrier();
-    ctx.hg().store().finish();
-    doc["section"] = strat->section_id();
-    doc["loop_iterations"] = opt.max_loop_iters;
-    return doc;
-  }
-
-  // DLNB_TIMELINE_EDGES=1 (with --timeline --graph): a stamp kernel on the
-  // launch stream before and after each timed graph launch (Timeline::edge;
-  // two more kernels per iteration, so off by default)
-  const bool tl_edges = env_int("DLNB_TIMELINE_EDGES", 0) != 0;
-  // Graph replays on a GPU (DLNB_PREARM=1, the default): the host runs one
-  // launch ahead. Iteration r+1's graph is enqueued while r runs, behind a
-  // one-wave kernel that holds the launch stream until the host stores r+2 in
-  // a host-coherent "go" word; a kernel after each graph stores r+1 in a
-  // "done" word the host polls (CompletionFlag). Each iteration is still
-  // timed alone, from the go store to the host seeing its done word, but its
-  // start no longer waits for hipGraphLaunch's submission after an idle
-  // device (~70 us) and its end not for hipStreamQuery (~20 us)
-  // (profiles/host_boundary_r4.md). Iteration 0 is armed before the timed
-  // region starts (as the last warm-up iteration would in a longer loop); all
-  // of its device work runs inside it, as does the loop's closing device
-  // synchronize. DLNB_PREARM=0: launch, then poll the streams (A/B).
-  // Lane graphs: every lane has its own go wait and done word; the host
-  // waits for all of them (the iteration ends when every stream has).
-  const size_t nlanes = lanes_ss.size();
-  const size_t nhs = 2 + nlanes;
-  uint64_t* hs = nullptr;  // [0] go, [1] go-wait timeouts, [2 + i] lane i done
-  if (replay && ctx.dev->kind() == DeviceKind::GPU && env_int("DLNB_PREARM", 1) != 0) hs = ctx.dev->alloc_stamps(nhs);
-  struct Handshake {
-    Device& d;
-    uint64_t*& p;
-    size_t n;
-    ~Handshake() {
-      if (std::uncaught_exceptions() != 0) {
-        // The run failed inside the timed loop: abort the device waits before
-        // anything is torn down - an armed replay is NOT released (its go
-        // wait sees the abort and lets it run through poisoned: no compute,
-        // no waits); a CLI process ends here (device_failure). The words are
-        // not freed (hipHostFree waits for the device, which may be hung).
-        device_failure("exception in the timed loop: " + last_error_message());
-        return;
-      }
-      if (p) d.free_stamps(p, n);
-    }
-  } handshake{*ctx.dev, hs, nhs};
-  // An armed replay waits for its go through the whole iteration before it:
-  // its wait's bound (after which it runs anyway, counted in
-  // prearm_go_timeouts) is 4x the compute floor + 60 s.
-  const double go_timeout_s =
-      std::max(60.0, 4.0 * strat->compute_floor_us(ctx) * 1e-6 * opt.time_scale + 60.0);
-  std::vector<uint64_t> armed_iter;  // device iteration number of each armed replay
-  auto arm = [&](int r) {
-    const uint64_t it = ++dev_iter;
-    armed_iter.push_back(it);
-    const auto& L = lanes_for(it);
-    for (size_t i = 0; i < nlanes; ++i) {
-      Stream& l = *L[i];
-      ctx.dev->host_wait(l, hs, static_cast<uint64_t>(r) + 1, go_timeout_s, hs + 1, it);
-      if (TL && tl_edges && i == 0) TL->edge(l, 0);
-      if (lane_graphs.empty())
-        graph->launch(l);
-      else
-        lane_graphs[i]->launch(l);
-      if (TL && tl_edges && i == 0) TL->edge(l, 1);
-      // (lane graphs signal from inside: their last node, lane_done)
-      if (!lane_done) ctx.dev->host_signal(l, hs + 2 + i, static_cast<uint64_t>(r) + 1);
-    }
-  };
   ctx.hg().barrier();
-  ctx.compute->reset_capped(*strat->streams()[0]);  // count the timed iterations only
+  ctx.hg().store().finish();
+  Json doc = Json::object();
+  doc["section"] = strat.section_id();
+  doc["loop_iterations"] = opt.max_loop_iters;
+  return doc;
+}
+
+// The timed runs: each iteration timed alone on the host. Pre-armed replays
+// (Replay::begin_timed) keep one launch ahead: between the go store and the
+// host seeing the done word there is only arm(r + 1) and the wait.
+void timed_loop(Context& ctx, Strategy& strat, RunSetup& su, Replay& replay, TimedRuns& tr) {
+  TimerSet& T = *strat.timers();
+  Timeline* TL = ctx.timeline.get();
+  EnergyMeter* meter = su.meter.get();
+  const int runs = tr.runs;
+  const char* rkey = su.rkey;
+  replay.begin_timed();
+  const bool prearm = replay.prearmed();
+  ctx.hg().barrier();
+  ctx.compute->reset_capped(*strat.streams()[0]);  // count the timed iterations only
   ctx.dev->synchronize();
-  // host time of each arm() (the launches of the next replay): a launch that
-  // blocks on the runtime shows up here (profiles/stall_r5.md)
-  std::vector<double> arm_s;
-  if (hs && runs > 0) arm(0);  // submitted, held until the first go
-  // clock / power at each iteration's end (the sampler thread's latest
-  // readings, and sclk's range over the iteration: VERDICT r5 #7)
-  std::vector<EnergyMeter::Sensors> sensors;
+  if (prearm && runs > 0) replay.arm(0);  // submitted, held until the first go
   {
     EnergyMeter::Sensors s0;
     meter->take(s0);  // the first window starts here
   }
   const double T0 = now_s();
   for (int r = 0; r < runs; ++r) {
-    fault.at_iteration(iter_no++, inject_task);
-    TraceRange tr("dlnb:iteration");
+    next_iteration(su, ctx, strat);
+    TraceRange trace("dlnb:iteration");
     const double j0 = meter->joules();
     double t0 = now_s();
-    if (hs) {
-      __atomic_store_n(hs, static_cast<uint64_t>(r) + 1, __ATOMIC_RELEASE);  // go
+    if (prearm) {
+      replay.go(r);
       if (r + 1 < runs) {
         const double a0 = now_s();
-        arm(r + 1);
-        arm_s.push_back(now_s() - a0);
+        replay.arm(r + 1);
+        tr.arm_s.push_back(now_s() - a0);
       }
-      if (lane_done) {
-        CompletionFlag cf(lane_done, joined ? 1 : lane_done_n, armed_iter.at(static_cast<size_t>(r)));
-        strat->synchronize();
-      } else {
-        CompletionFlag cf(hs + 2, nlanes, static_cast<uint64_t>(r) + 1);
-        strat->synchronize();
-      }
+      replay.wait_armed(r);
     } else {
-      if (TL && replay && tl_edges) TL->edge(*origin, 0);
-      enqueue();
-      if (TL && replay && tl_edges) TL->edge(*origin, 1);
-      wait_iteration();
+      replay.enqueue_timed();
+      replay.wait_iteration();
     }
     const double t1 = now_s();
     T.add(rkey, t1 - t0);
@@ -1172,243 +775,74 @@ Json run_rank_impl(const Options& opt, Context& ctx, std::unique_ptr<Strategy>& 
     }
     if (meter->available()) T.add("energy_consumed", meter->joules() - j0);
     EnergyMeter::Sensors sn;
-    if (meter->take(sn)) sensors.push_back(sn);
+    if (meter->take(sn)) tr.sensors.push_back(sn);
   }
   ctx.dev->synchronize();
   ctx.hg().barrier();
-  const double timed_region = ctx.hg().allreduce_max(now_s() - T0);
+  tr.timed_region_s = ctx.hg().allreduce_max(now_s() - T0);
+}
+
+// --timeline: gathers every rank's spans (rank 0 writes the trace file) and
+// returns the report's `timeline` block.
+Json gather_timeline(Context& ctx, const std::string& backend) {
+  const Options& opt = ctx.opt;
+  const RankInfo& ri = ctx.boot->info;
+  Json mine = ctx.timeline->rank_json(ri.rank, opt.timeline_iters);
+  mine["device"] = ctx.dev->name() + " " + std::to_string(ctx.dev->index()) + " @ " + ri.hostname;
+  auto parts = ctx.hg().allgather(mine.dump());
+  Json timeline_info = Json::object();
+  timeline_info["path"] = opt.timeline_path;
+  timeline_info["iterations_kept"] = opt.timeline_iters;
+  long long nev = 0;
+  bool trunc = false;
+  std::vector<Json> docs;
+  for (const auto& p : parts) {
+    docs.push_back(Json::parse(p));
+    nev += static_cast<long long>(docs.back().at("events").size());
+    trunc = trunc || docs.back().at("truncated").as_bool();
+  }
+  timeline_info["events"] = nev;
+  timeline_info["truncated"] = trunc;
+  if (ri.rank == 0) {
+    Json meta = Json::object();
+    meta["strategy"] = strategy_name(opt.strategy);
+    meta["model"] = opt.model;
+    meta["backend"] = backend;
+    meta["graph"] = opt.graph;
+    meta["world_size"] = ri.world_size;
+    write_chrome_trace(opt.timeline_path, docs, meta);
+  }
+  return timeline_info;
+}
+
+// setup -> replay build -> warm-up -> (loop mode | timed loop) -> report
+Json run_rank_impl(const Options& opt, Context& ctx, std::unique_ptr<Strategy>& strat) {
+  const RankInfo& ri = ctx.boot->info;
+  RunSetup su = setup_rank(opt, ctx, strat);
+  Replay replay(ctx, *strat, su.backend);
+  if (opt.graph) replay.build();
+  ctx.hg().barrier();
+
+  TimedRuns tr;
+  warm_up(ctx, *strat, su, replay, tr.warm);
+  tr.runs = opt.min_exectime > 0 ? estimate_runs(ctx, tr.warm) : opt.runs;
+  if (opt.loop) return loop_mode(ctx, *strat, su, replay);
+  timed_loop(ctx, *strat, su, replay, tr);
   if (!opt.dump_outputs.empty()) dump_outputs(ctx, *strat, opt.dump_outputs);
 
-  // ---- report
-  Json rank = strat->rank_json();
-  if (hs) {
-    rank["prearm_go_timeouts"] = static_cast<double>(__atomic_load_n(hs + 1, __ATOMIC_ACQUIRE));
-    Json a = Json::array();
-    for (double x : arm_s) a.push_back(x * 1e3);
-    rank["prearm_launch_ms"] = a;
-  }
-  rank["energy_consumed"] = T.values_json("energy_consumed");
-  if (!sensors.empty()) {
-    Json c = Json::array(), lo = Json::array(), hi = Json::array(), w = Json::array();
-    for (const auto& x : sensors) {
-      c.push_back(x.sclk_mhz);
-      lo.push_back(x.sclk_min_mhz);
-      hi.push_back(x.sclk_max_mhz);
-      w.push_back(x.power_w);
-    }
-    rank["iteration_sclk_mhz"] = c;
-    rank["iteration_sclk_min_mhz"] = lo;
-    rank["iteration_sclk_max_mhz"] = hi;
-    rank["iteration_power_w"] = w;
-  }
-  {
-    // the duration of each timed iteration's last collective (ms)
-    const std::string tk = strat->tail_collective_timer();
-    const auto& v = tk.empty() ? std::vector<double>() : T.get(tk);
-    if (runs > 0 && !v.empty() && v.size() % static_cast<size_t>(runs) == 0) {
-      const size_t per = v.size() / static_cast<size_t>(runs);
-      Json a = Json::array();
-      for (int r = 0; r < runs; ++r) a.push_back(v[(static_cast<size_t>(r) + 1) * per - 1] * 1e3);
-      rank["iteration_last_collective_ms"] = a;
-      rank["iteration_last_collective"] = tk;
-    }
-  }
-  {
-    // chained deadline tasks: lateness absorbed (<= the cap each) and beyond
-    // the cap (deadline_sync.hpp), gate waits that timed out
-    ComputeEngine::ChainCounters cc;
-    if (runs > 0 && ctx.compute->chain_counters(cc)) {
-      Json c = Json::object();
-      c["tasks_per_iter"] = cc.capped_tasks / runs;
-      c["ms_per_iter"] = cc.capped_s / runs * 1e3;
-      c["absorbed_tasks_per_iter"] = cc.absorbed_tasks / runs;
-      c["absorbed_ms_per_iter"] = cc.absorbed_s / runs * 1e3;
-      // device gate waits that gave up at their bound (never expected): a comm
-      // lane's gate_wait, a deadline task's gate, a gate event's wait
-      c["gate_wait_timeouts"] = cc.wait_timeouts + static_cast<double>(ctx.dev->gate_event_timeouts());
-      c["compute_gate_timeouts"] = cc.gate_timeouts;
-      // waits that left on the host's abort word, program blocks that came late for a task
-      c["aborted_waits"] = cc.aborted;
-      c["late_blocks"] = cc.late_blocks;
-      rank["chain_capped"] = c;
-    }
-  }
-  // intervals whose stamps came out of order (recorded as 0; never expected)
-  if (T.has_negatives()) rank["timer_negative_intervals"] = T.negatives_json();
-  rank["hostname"] = ri.hostname;
-  rank["rank"] = ri.rank;
-  rank["local_rank"] = ri.local_rank;
-  rank["device_name"] = ctx.dev->name();
-  rank["device_index"] = ctx.dev->index();
-  rank["comm"] = strat->comm_summary();
-  // Fixed-work compute: measured task time / uncontended (table) time over
-  // the timed runs. > 1 means the collectives running beside the compute
-  // (HBM traffic, CUs, power) slowed it down.
-  const double task_s = T.sum("compute_task_time"), table_s = T.sum("compute_task_table");
-  if (!T.get("compute_task_time").empty() && table_s > 0) {
-    rank["compute_stretch"] = task_s / table_s;
-    rank["compute_task_s"] = task_s;
-    rank["compute_table_s"] = table_s;
-  }
-  auto all = ctx.hg().allgather(rank.dump());
+  auto all = ctx.hg().allgather(rank_report(ctx, *strat, tr, replay).dump());
   Json timeline_info = nullptr;
-  if (TL) {
-    Json mine = TL->rank_json(ri.rank, opt.timeline_iters);
-    mine["device"] = ctx.dev->name() + " " + std::to_string(ctx.dev->index()) + " @ " + ri.hostname;
-    auto parts = ctx.hg().allgather(mine.dump());
-    timeline_info = Json::object();
-    timeline_info["path"] = opt.timeline_path;
-    timeline_info["iterations_kept"] = opt.timeline_iters;
-    long long nev = 0;
-    bool trunc = false;
-    std::vector<Json> docs;
-    for (const auto& p : parts) {
-      docs.push_back(Json::parse(p));
-      nev += static_cast<long long>(docs.back().at("events").size());
-      trunc = trunc || docs.back().at("truncated").as_bool();
-    }
-    timeline_info["events"] = nev;
-    timeline_info["truncated"] = trunc;
-    if (ri.rank == 0) {
-      Json meta = Json::object();
-      meta["strategy"] = strategy_name(opt.strategy);
-      meta["model"] = opt.model;
-      meta["backend"] = backend;
-      meta["graph"] = opt.graph;
-      meta["world_size"] = ri.world_size;
-      write_chrome_trace(opt.timeline_path, docs, meta);
-    }
-  }
-
-  Json g = strat->global_json();
-  Json ext = Json::object();
-  ext["strategy"] = strategy_name(opt.strategy);
-  ext["schedule"] = opt.schedule;
-  {
-    size_t nodes = graph ? graph->nodes() : 0;
-    for (const auto& g : lane_graphs) nodes += g->nodes();
-    ext["graph"] = static_cast<double>(nodes);
-  }
-  if (opt.graph) ext["lane_graphs"] = lane_info;
-  // pre-armed replay loop (each iteration's launch submitted during the one
-  // before, released by a host store; DLNB_PREARM=0 launches in the loop)
-  ext["prearm"] = hs != nullptr;
-  ext["wire_dtype"] = dtype_name(ctx.wire);
-  ext["compute"] = ctx.compute->describe();
-  ext["stats_file"] = stats_path;
-  ext["stats_dtype"] = ctx.stats.dtype;
-  ext["stats_device"] = ctx.stats.device;
-  ext["warmup"] = opt.warmup;
-  ext["runs"] = runs;
-  ext["warmup_times"] = Json(warm);
-  ext["timed_region_s"] = timed_region;
-  ext["energy_source"] = meter->source();
-  // ranks of this job on this rank's device (> 1: loopback threads or -d 0,0;
-  // the deadline compute then runs in 500-us slices, compute.cpp)
-  ext["ranks_on_device"] = ctx.ranks_on_device;
-  if (TL) ext["timeline"] = timeline_info;
-  {
-    Json b = Json::object();
-    b["lanes"] = lanes;
-    b["comm_cus"] = opt.comm_cus;
-    b["max_ctas_per_lane"] = ctx.lane_ctas;  // 0 = RCCL default
-    b["applies"] = rccl;
-    b["fits"] = !rccl || !gemm_compute || ctx.lane_ctas == 0 ? true : lanes * ctx.lane_ctas <= opt.comm_cus;
-    if (backend == "xgmi" || backend == "mixed") {
-      // xgmi kernels: blocks per lane = blocks_per_cu x max_ctas, so a lane
-      // occupies max_ctas CUs at the measured occupancy
-      const int bpc = xgmi::min_blocks_per_cu();
-      b["xgmi_blocks_per_cu"] = bpc;
-      b["xgmi_blocks_per_lane"] = ctx.lane_ctas > 0 ? bpc * ctx.lane_ctas : 0;
-    }
-    ext["rccl_cta_budget"] = b;
-  }
-  {
-    Json cl = comm_log_json(ctx.comm_log);
-    ext["communicators"] = cl.at("communicators");
-    ext["rccl_nranks"] = cl.at("rccl_nranks");
-    if (ctx.dev->kind() == DeviceKind::GPU) ext["runtime"] = runtime_info();
-  }
-  {
-    // Collective-library knobs of this run (the reference recorded them as
-    // SbatchMan job variables, plots/parser.py:151-154).
-    Json env = Json::object();
-    for (char** e = environ; e && *e; ++e) {
-      std::string kv = *e;
-      if (starts_with(kv, "NCCL_") || starts_with(kv, "RCCL_") || starts_with(kv, "HSA_") || starts_with(kv, "DLNB_")) {
-        size_t eq = kv.find('=');
-        if (eq != std::string::npos) env[kv.substr(0, eq)] = kv.substr(eq + 1);
-      }
-    }
-    ext["env"] = env;
-  }
-  // Iteration time = max over ranks per run (the slowest rank bounds a step).
-  std::vector<Json> ranks;
-  for (const auto& s : all) ranks.push_back(Json::parse(s));
-  std::vector<double> per_run(static_cast<size_t>(runs), 0.0);
-  for (const auto& rj : ranks) {
-    const Json& v = rj.at(rkey);
-    for (size_t i = 0; i < v.size() && i < per_run.size(); ++i) per_run[i] = std::max(per_run[i], v.at(i).as_double());
-  }
-  Json it = Json::object();
-  it["per_run_max_s"] = Json(per_run);
-  it["median_ms"] = percentile(per_run, 0.5) * 1e3;
-  double mean = 0;
-  for (double x : per_run) mean += x;
-  it["mean_ms"] = per_run.empty() ? 0.0 : mean / per_run.size() * 1e3;
-  it["p95_ms"] = percentile(per_run, 0.95) * 1e3;
-  it["min_ms"] = per_run.empty() ? 0.0 : *std::min_element(per_run.begin(), per_run.end()) * 1e3;
-  it["timed_ms_per_iter"] = runs > 0 ? timed_region / runs * 1e3 : 0.0;
-  double floor_us = strat->compute_floor_us(ctx);
-  it["compute_floor_ms"] = floor_us / 1e3 * opt.time_scale;
-  ext["iteration"] = it;
-  {
-    double worst = 0;
-    for (const auto& rj : ranks)
-      if (rj.contains("compute_stretch")) worst = std::max(worst, rj.at("compute_stretch").as_double());
-    if (worst > 0) ext["compute_stretch"] = worst;  // max over ranks
-    // Compute tasks that waited beyond the chain's absorb cap per iteration
-    // (the wait stays in the iteration time; max over ranks)
-    double ctasks = -1, cms = 0, gto = 0, cgto = 0, ams = 0, atasks = 0;
-    for (const auto& rj : ranks)
-      if (rj.contains("chain_capped")) {
-        const Json& c = rj.at("chain_capped");
-        ctasks = std::max(ctasks, c.at("tasks_per_iter").as_double());
-        cms = std::max(cms, c.at("ms_per_iter").as_double());
-        gto = std::max(gto, c.at("gate_wait_timeouts").as_double());
-        cgto = std::max(cgto, c.at("compute_gate_timeouts").as_double());
-        ams = std::max(ams, c.at("absorbed_ms_per_iter").as_double());
-        atasks = std::max(atasks, c.at("absorbed_tasks_per_iter").as_double());
-      }
-    if (ctasks >= 0) {
-      Json c = Json::object();
-      c["tasks_per_iter_max"] = ctasks;
-      c["ms_per_iter_max"] = cms;
-      c["gate_wait_timeouts_max"] = gto;
-      c["compute_gate_timeouts_max"] = cgto;
-      // lateness the chained tasks took out of their own compute (launch
-      // hops, drains): invisible in the iteration time, shown here
-      c["absorbed_ms_per_iter_max"] = ams;
-      c["absorbed_tasks_per_iter_max"] = atasks;
-      ext["chain_capped"] = c;
-    }
-  }
-  g["dlnb"] = ext;
-
-  doc["section"] = strat->section_id();
-  doc["title"] = strat->section_title();
-  doc["global"] = g;
-  Json rarr = Json::array();
-  for (auto& r : ranks) rarr.push_back(r);
-  doc["ranks"] = rarr;
+  if (ctx.timeline) timeline_info = gather_timeline(ctx, su.backend);
+  Json doc = global_report(ctx, *strat, su, tr, replay, all, timeline_info);
 
   if (ri.rank == 0 && !opt.silent) {
     std::string text = doc.dump();
     std::cout << "<<<DLNB_REPORT_BEGIN " << strat->section_id() << ">>>\n"
               << text << "\n<<<DLNB_REPORT_END " << strat->section_id() << ">>>" << std::endl;
     if (!opt.quiet) {
+      const Json& it = doc.at("global").at("dlnb").at("iteration");
       std::printf("[dlnb] %s %s W=%d backend=%s compute=%s: iter median %.3f ms (floor %.3f ms), timed %.3f ms/iter\n",
-                  strategy_name(opt.strategy), opt.model.c_str(), ri.world_size, backend.c_str(),
+                  strategy_name(opt.strategy), opt.model.c_str(), ri.world_size, su.backend.c_str(),
                   compute_mode_name(ctx.compute->mode()), it.at("median_ms").as_double(),
                   it.at("compute_floor_ms").as_double(), it.at("timed_ms_per_iter").as_double());
       std::fflush(stdout);

@@ -89,9 +89,6 @@ class Pipeline : public Strategy {
     E_ = has_ep_ ? o.num_expert_shards : 1;
     inner_ = T_ * E_;  // TP fastest, then EP (hybrid_4d), then stage, then DP replica
     reference_ = o.schedule == "reference";
-    // A/B: the round-5 placement of the TP / EP collectives (on the compute
-    // stream between the tasks) instead of the inner lane
-    inner_on_compute_ = env_int("DLNB_INNER_ON_COMPUTE", 0) != 0;
     one_f_one_b_ = o.pp_schedule == "1f1b";
     interleaved_ = o.pp_schedule == "interleaved";
     dualpipe_ = o.pp_schedule == "dualpipe";
@@ -1061,7 +1058,7 @@ class Pipeline : public Strategy {
     // graph or eager they stay on the compute stream. Ranks sharing a GPU
     // (4 over xgmi, profiles/pipeline_program_r6.md): the inner lane ran C3
     // 795 against 810 ms and C4 2802 against 379 ms on the compute stream.
-    inner_lane_ = !inner_on_compute_ && ctx_->dev->gate_events();
+    inner_lane_ = ctx_->dev->gate_events();
     prog_ = ctx_->dev->gate_events() && !reference_ && program_ok() && ctx_->compute->begin_program(*compute_);
     if (dualpipe_)
       enqueue_dualpipe();
@@ -1103,8 +1100,6 @@ class Pipeline : public Strategy {
   }
   // DualPipe takes the single graph (below).
   bool program_ok() const {
-    const int forced = env_int("DLNB_PIPELINE_PROGRAM", -1);  // A/B: 0 never, 1 always (lane graphs)
-    if (forced >= 0) return forced != 0;
     return !(has_tp_ && T_ > 1) && !(has_ep_ && E_ > 1) && !dualpipe_;
   }
 
@@ -1246,7 +1241,6 @@ class Pipeline : public Strategy {
   bool has_tp_ = false, has_ep_ = false, sp_ = false;
   uint64_t tp_shard_ = 0;  // ceil(tp_ar_ / T): sequence-parallel shard
   bool reference_ = false;
-  bool inner_on_compute_ = false;
   bool inner_lane_ = false;  // this enqueue puts the TP / EP collectives on the inner lane
   bool one_f_one_b_ = false, interleaved_ = false, dualpipe_ = false;
   std::vector<std::vector<DpOp>> dp_ticks_;  // [tick][stage]

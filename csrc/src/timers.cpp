@@ -40,11 +40,6 @@ const uint64_t* TimerSet::end(int token, Stream& s, const std::string& name) {
 }
 
 void TimerSet::stall(Stream& s, Event& e, const std::string& name) {
-  static const bool timed = env_int("DLNB_STALL_TIMERS", 1) != 0;  // 0: A/B the stamps' own cost
-  if (!timed) {
-    s.wait(e);
-    return;
-  }
   // A stamp-wait-stamp pair read short under graph replay (round 4): inside a
   // capture every stall is timed from task stamps (stall_before_task /
   // stall_after_task) or as a gap between stamps nothing waits between.
