@@ -126,8 +126,33 @@ class Strategy {
   TimerSet* timers() { return timers_.get(); }
 
  protected:
+  // The iteration's tail when the DP lane's last collective (end stamp
+  // dp_end) is all the compute stream still depends on. With a compute
+  // program (prog) and nothing after it on the compute stream (no optimizer),
+  // the program's join ends the iteration once the other lanes are done, and
+  // the DP tail exposed is the DP lane's last end stamp minus the compute's
+  // last task (a gap: no wait on the compute stream); otherwise the compute
+  // stream waits for the DP lane (dp_done, recorded here). Ends the program.
+  void join_or_stall_tail(Context& ctx, Stream& compute, bool prog, Stream& dp_lane, Event& dp_done,
+                          const uint64_t* dp_end);
   std::unique_ptr<TimerSet> timers_;
 };
+
+// One timed operation on a stream: begin(s), the operation, end(.., name).
+// Returns the end stamp.
+template <class Op>
+const uint64_t* timed(TimerSet& t, Stream& s, const char* name, Op&& op) {
+  const int token = t.begin(s);
+  op();
+  return t.end(token, s, name);
+}
+
+// A buffer that the collectives of `c` read or write: peer memory registered
+// with c when its backend moves data with its own kernels (xgmi, zero-copy),
+// plain device memory otherwise. Registration is in call order, and xgmi pairs
+// the k-th registration of every member: every member calls this in the same
+// order per communicator.
+Buffer comm_buffer(Device& dev, Communicator& c, size_t bytes);
 
 std::unique_ptr<Strategy> make_dp();
 std::unique_ptr<Strategy> make_fsdp();

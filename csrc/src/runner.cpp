@@ -161,6 +161,25 @@ Json comm_stats_json(const std::vector<CommStat>& stats, const TimerSet& t) {
   return out;
 }
 
+Buffer comm_buffer(Device& dev, Communicator& c, size_t bytes) {
+  if (!c.wants_peer_buffers()) return dev.alloc(bytes);
+  Buffer b = dev.alloc_peer(bytes);
+  c.register_buffer(b.data(), bytes);
+  return b;
+}
+
+void Strategy::join_or_stall_tail(Context& ctx, Stream& compute, bool prog, Stream& dp_lane, Event& dp_done,
+                                  const uint64_t* dp_end) {
+  const bool join = prog && !ctx.opt.optimizer && dp_end && timers_->task_stamps();
+  if (prog) ctx.compute->end_program(compute, join);
+  if (join) {
+    timers_->stall_until(compute, dp_end, "dp_exposed_time");
+  } else {
+    dp_lane.record(dp_done);
+    timers_->stall_after_task(compute, dp_done, "dp_exposed_time");
+  }
+}
+
 void optimizer_step(Context& ctx, Stream& s, void* param, void* mom, const void* grad, size_t n, uint64_t* end_stamp,
                     uint32_t* done) {
   if (ctx.dev->kind() == DeviceKind::GPU) {

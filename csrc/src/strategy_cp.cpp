@@ -113,17 +113,12 @@ class ContextParallel : public Strategy {
       } else {
         a2a_send_ = dev.alloc(C_ * std::max(qkv_peer_, out_peer_) * es_);
         // zero-copy (xgmi): peers write their blocks straight into a2a_recv_
-        const bool peer = cp_comm_->wants_peer_buffers();
-        const size_t rb = C_ * std::max(qkv_peer_, out_peer_) * es_;
-        a2a_recv_ = peer ? dev.alloc_peer(rb) : dev.alloc(rb);
-        if (peer) cp_comm_->register_buffer(a2a_recv_.data(), rb);
+        a2a_recv_ = comm_buffer(dev, *cp_comm_, C_ * std::max(qkv_peer_, out_peer_) * es_);
         dev.fill_random(a2a_send_.data(), C_ * std::max(qkv_peer_, out_peer_), ctx.wire, 5100, *compute_);
       }
     }
-    const bool dp_peer = dp_comm_->wants_peer_buffers();  // in-place bucket all-reduces, zero-copy on xgmi
     for (int b = 0; b < nbk_; ++b) {
-      grads_.push_back(dp_peer ? dev.alloc_peer(bucket_[b] * es_) : dev.alloc(bucket_[b] * es_));
-      if (dp_peer) dp_comm_->register_buffer(grads_.back().data(), bucket_[b] * es_);
+      grads_.push_back(comm_buffer(dev, *dp_comm_, bucket_[b] * es_));  // in-place bucket all-reduces, zero-copy on xgmi
       dev.fill_random(grads_.back().data(), bucket_[b], ctx.wire, 5200 + b, *compute_);
       bucket_ready_.push_back(dev.create_event());
     }
@@ -199,9 +194,8 @@ class ContextParallel : public Strategy {
   void ulysses_a2a(uint64_t per_peer, const char* tk) {
     compute_->record(*proj_done_);
     cp_stream_->wait(*proj_done_);
-    int t = timers_->begin(*cp_stream_);
-    cp_comm_->all_to_all(a2a_send_.data(), a2a_recv_.data(), per_peer, ctx_->wire, *cp_stream_);
-    timers_->end(t, *cp_stream_, tk);
+    timed(*timers_, *cp_stream_, tk,
+          [&] { cp_comm_->all_to_all(a2a_send_.data(), a2a_recv_.data(), per_peer, ctx_->wire, *cp_stream_); });
     cp_stream_->record(*a2a_done_);
     timers_->stall_before_task(*compute_, *a2a_done_, "cp_exposed_time");
   }
@@ -229,22 +223,13 @@ class ContextParallel : public Strategy {
       if ((i + 1) * nbk_ / L_ > b) {  // last layer of bucket b done
         compute_->record(*bucket_ready_[b]);
         dp_stream_->wait(*bucket_ready_[b]);
-        int t = timers_->begin(*dp_stream_);
-        dp_comm_->all_reduce(grads_[b].data(), grads_[b].data(), bucket_[b], ctx.wire, *dp_stream_);
-        dp_end = timers_->end(t, *dp_stream_, "dp_comm_time");
+        dp_end = timed(*timers_, *dp_stream_, "dp_comm_time", [&] {
+          dp_comm_->all_reduce(grads_[b].data(), grads_[b].data(), bucket_[b], ctx.wire, *dp_stream_);
+        });
         ++b;
       }
     }
-    // nothing after the program on the compute stream (no optimizer): it ends
-    // in the lane join and the DP tail is a gap (as the pipeline's)
-    const bool join = prog && !ctx.opt.optimizer && dp_end && timers_->task_stamps();
-    if (prog) ce.end_program(*compute_, join);
-    if (join) {
-      timers_->stall_until(*compute_, dp_end, "dp_exposed_time");
-    } else {
-      dp_stream_->record(*dp_done_);
-      timers_->stall_after_task(*compute_, *dp_done_, "dp_exposed_time");
-    }
+    join_or_stall_tail(ctx, *compute_, prog, *dp_stream_, *dp_done_, dp_end);
     if (ctx.opt.optimizer) {
       size_t off = 0;
       for (int k = 0; k < nbk_; ++k) {

@@ -123,12 +123,7 @@ class DataParallel : public Strategy {
     // Zero-copy (xgmi): gradient buckets and all-reduce outputs in peer
     // memory, registered with the communicator, so the collectives read and
     // write peers' buffers directly (see Communicator::register_buffer).
-    const bool peer = comm_->wants_peer_buffers();
-    auto buf = [&](size_t bytes, bool reg) {
-      Buffer b = peer && reg ? dev.alloc_peer(bytes) : dev.alloc(bytes);
-      if (peer && reg) comm_->register_buffer(b.data(), bytes);
-      return b;
-    };
+    auto buf = [&](size_t bytes, bool reg) { return reg ? comm_buffer(dev, *comm_, bytes) : dev.alloc(bytes); };
     for (int i = 0; i < nb_; ++i) {
       const uint64_t n = zero_ ? shard_[i] * W_ : sizes_[i];  // padded for ZeRO
       grads_.push_back(buf(n * es_, true));

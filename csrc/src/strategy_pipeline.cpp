@@ -76,8 +76,36 @@ class Pipeline : public Strategy {
  public:
   explicit Pipeline(StrategyKind k) : kind_(k) {}
 
+  // The order matters across ranks: every member of a group creates its
+  // communicators, and registers its buffers with them, in the same order.
   void setup(Context& ctx) override {
     ctx_ = &ctx;
+    check_arguments();
+    message_sizes();
+    if (dualpipe_) build_dualpipe();
+    create_communicators();
+    allocate_buffers_and_events();
+    declare_timers_and_stats();
+  }
+
+  // A stage's link to one neighbour: a 2-rank communicator on a stream of its
+  // own. What it sends is double buffered, as is what it receives; the event
+  // vectors order the buffers' reuse against the compute stream.
+  struct Link {
+    using Events = std::vector<std::unique_ptr<Event>>;
+    std::unique_ptr<Communicator> comm;
+    std::unique_ptr<Stream> stream;
+    int peer = 0;                // the neighbour's index in comm
+    Buffer send[2], recv[2];     // slot i uses buffer i & 1
+    Events* produced = nullptr;  // waited on before a send: the compute step that wrote send[i & 1]
+    Events* consumed = nullptr;  // waited on before receive i: step i - 2, the last reader of recv[i & 1]
+    Events* sent = nullptr;      // recorded after a send
+    Events* recvd = nullptr;     // recorded after a receive
+    explicit operator bool() const { return comm != nullptr; }
+  };
+
+  void check_arguments() {
+    Context& ctx = *ctx_;
     const auto& o = ctx.opt;
     const auto& st = ctx.stats;
     const int W = ctx.world();
@@ -131,7 +159,12 @@ class Pipeline : public Strategy {
     tp_id_ = inner_id_ % T_;
     ep_id_ = inner_id_ / T_;
     dp_id_ = c.dp_id;
+  }
 
+  // Elements per message and compute per microbatch (the file header).
+  void message_sizes() {
+    const auto& o = ctx_->opt;
+    const auto& st = ctx_->stats;
     spmb_ = st.batch_size / mb_;
     pipe_ = st.seq_len * st.embedded_dim * spmb_;
     double tshard = T_;
@@ -180,43 +213,36 @@ class Pipeline : public Strategy {
     }
     sp_ = has_tp_ && o.sequence_parallel;
     tp_shard_ = has_tp_ ? (tp_ar_ + T_ - 1) / T_ : 0;
+    es_ = dtype_size(ctx_->wire);
+  }
+
+  // The link communicator of stages `from` -> `to` of this pipeline (pp: its
+  // ranks by stage), on its two members: `from` keeps it as its next link,
+  // `to` as its previous one.
+  void create_link(const std::string& name, const std::vector<int>& pp, int from, int to) {
+    if (stage_ != from && stage_ != to) return;
+    Context& ctx = *ctx_;
+    Link& l = stage_ == from ? next_ : prev_;
+    l.comm = ctx.comms->create(name, {pp[from], pp[to]}, pipe_ * es_, true, ctx.lane_ctas);
+    l.peer = stage_ == from ? 1 : 0;
+  }
+
+  void create_communicators() {
+    Context& ctx = *ctx_;
+    const auto& o = ctx.opt;
     Device& dev = *ctx.dev;
-    es_ = dtype_size(ctx.wire);
     const int rank = ctx.rank();
     compute_ = dev.create_stream(false);
     std::vector<int> pp = pp_group(rank, inner_, S_);
     // Link communicators between adjacent stages of this pipeline. Created
     // in stage order by every member so creation never deadlocks.
-    for (int s = 0; s + 1 < S_; ++s) {
-      if (stage_ == s || stage_ == s + 1) {
-        std::string nm = "pp/link/" + std::to_string(dp_id_) + "/" + std::to_string(inner_id_) + "/" + std::to_string(s);
-        auto comm = ctx.comms->create(nm, {pp[s], pp[s + 1]}, pipe_ * es_, true, ctx.lane_ctas);
-        if (stage_ == s) {
-          next_ = std::move(comm);
-          next_peer_ = 1;
-        } else {
-          prev_ = std::move(comm);
-          prev_peer_ = 0;
-        }
-      }
-    }
-    if (interleaved_ && S_ > 1) {
-      // The interleaved schedule's ring closes: chunk c of the last stage
-      // feeds chunk c+1 of stage 0 over a wrap link.
-      if (stage_ == S_ - 1 || stage_ == 0) {
-        std::string nm = "pp/wrap/" + std::to_string(dp_id_) + "/" + std::to_string(inner_id_);
-        auto comm = ctx.comms->create(nm, {pp[S_ - 1], pp[0]}, pipe_ * es_, true, ctx.lane_ctas);
-        if (stage_ == S_ - 1) {
-          next_ = std::move(comm);
-          next_peer_ = 1;
-        } else {
-          prev_ = std::move(comm);
-          prev_peer_ = 0;
-        }
-      }
-    }
-    if (prev_) prev_stream_ = dev.create_stream(true);
-    if (next_) next_stream_ = dev.create_stream(true);
+    const std::string of = std::to_string(dp_id_) + "/" + std::to_string(inner_id_);
+    for (int s = 0; s + 1 < S_; ++s) create_link("pp/link/" + of + "/" + std::to_string(s), pp, s, s + 1);
+    // The interleaved schedule's ring closes: chunk c of the last stage
+    // feeds chunk c+1 of stage 0 over a wrap link.
+    if (interleaved_ && S_ > 1) create_link("pp/wrap/" + of, pp, S_ - 1, 0);
+    for (Link* l : {&prev_, &next_})
+      if (*l) l->stream = dev.create_stream(true);
     {
       // TP group: same (dp, stage, ep); EP group: same (dp, stage, tp). With
       // one of the two degrees = 1 these are the reference's inner groups
@@ -245,7 +271,8 @@ class Pipeline : public Strategy {
     {
       std::string nm = "dp/" + std::to_string(stage_) + "/" + std::to_string(inner_id_);
       const int nbk = o.dp_buckets;
-      dp_comm_ = ctx.comms->create(nm, dp_group(rank, inner_, S_, W), (dp_ar_ / nbk + 1) * es_, false, ctx.lane_ctas);
+      dp_comm_ = ctx.comms->create(nm, dp_group(rank, inner_, S_, ctx.world()), (dp_ar_ / nbk + 1) * es_, false,
+                                   ctx.lane_ctas);
       dp_stream_ = dev.create_stream(true);
     }
     if (dualpipe_) {
@@ -256,34 +283,31 @@ class Pipeline : public Strategy {
       mirror_comm_ = ctx.comms->create("pp/mirror/" + std::to_string(dp_id_) + "/" + std::to_string(inner_id_) + "/" +
                                            std::to_string(lo),
                                        pair, dp_ar_ * es_, false, ctx.lane_ctas);
-      build_dualpipe();
+    }
+  }
+
+  void allocate_buffers_and_events() {
+    Context& ctx = *ctx_;
+    const auto& o = ctx.opt;
+    Device& dev = *ctx.dev;
+    if (dualpipe_) {
       for (int k = 0; k < 2 * mb_; ++k) dpbuf_.push_back(dev.alloc(pipe_ * es_));
       mirror_ready_ = dev.create_event();
     }
-
-    // Buffers.
-    for (int b = 0; b < 2; ++b) {
-      if (prev_) {
-        act_in_[b] = dev.alloc(pipe_ * es_);
-        grad_out_[b] = dev.alloc(pipe_ * es_);
-        dev.fill_random(grad_out_[b].data(), pipe_, ctx.wire, 4000 + b, *compute_);
+    // The previous link sends gradients (seeds 4000, 4001) and receives
+    // activations; the next link sends activations (4100, 4101).
+    for (int b = 0; b < 2; ++b)
+      for (Link* l : {&prev_, &next_}) {
+        if (!*l) continue;
+        l->recv[b] = dev.alloc(pipe_ * es_);
+        l->send[b] = dev.alloc(pipe_ * es_);
+        dev.fill_random(l->send[b].data(), pipe_, ctx.wire, (l == &prev_ ? 4000 : 4100) + b, *compute_);
       }
-      if (next_) {
-        act_out_[b] = dev.alloc(pipe_ * es_);
-        grad_in_[b] = dev.alloc(pipe_ * es_);
-        dev.fill_random(act_out_[b].data(), pipe_, ctx.wire, 4100 + b, *compute_);
-      }
-    }
     // Zero-copy (xgmi): the DP gradient (and its all-reduce output) and the
     // expert receive buffer are peer memory registered with their groups.
-    const bool dp_peer = dp_comm_->wants_peer_buffers();
-    grad_ = dp_peer ? dev.alloc_peer(dp_ar_ * es_) : dev.alloc(dp_ar_ * es_);
+    grad_ = comm_buffer(dev, *dp_comm_, dp_ar_ * es_);
     dev.fill_random(grad_.data(), dp_ar_, ctx.wire, 4200, *compute_);
-    if (!o.in_place) sum_grad_ = dp_peer ? dev.alloc_peer(dp_ar_ * es_) : dev.alloc(dp_ar_ * es_);
-    if (dp_peer) {
-      dp_comm_->register_buffer(grad_.data(), grad_.bytes());
-      if (!o.in_place) dp_comm_->register_buffer(sum_grad_.data(), sum_grad_.bytes());
-    }
+    if (!o.in_place) sum_grad_ = comm_buffer(dev, *dp_comm_, dp_ar_ * es_);
     if (has_tp_) {
       tp_buf_ = dev.alloc(tp_shard_ * T_ * es_);
       tp_res_ = dev.alloc(tp_shard_ * T_ * es_);
@@ -293,9 +317,7 @@ class Pipeline : public Strategy {
       // skew: the hot rank receives E_ * skew_counts_[0] in a dispatch
       const uint64_t n = skew_counts_.empty() ? a2a_ * E_ : std::max<uint64_t>(a2a_ * E_, skew_counts_[0] * E_);
       ep_send_ = dev.alloc(n * es_);
-      const bool ep_peer = ep_comm_->wants_peer_buffers();
-      ep_recv_ = ep_peer ? dev.alloc_peer(n * es_) : dev.alloc(n * es_);
-      if (ep_peer) ep_comm_->register_buffer(ep_recv_.data(), ep_recv_.bytes());
+      ep_recv_ = comm_buffer(dev, *ep_comm_, n * es_);
       dev.fill_random(ep_send_.data(), a2a_ * E_, ctx.wire, 4400, *compute_);
       if (ep_overlap_) {
         // The half-microbatch all-to-alls share the DP lane instead of a
@@ -331,13 +353,25 @@ class Pipeline : public Strategy {
     mk(recv_b_);
     mk(bwd_done_);
     mk(send_b_);
+    // previous link: gradients out, activations in; next link: activations out, gradients in
+    prev_.produced = &bwd_done_;
+    prev_.sent = &send_b_;
+    prev_.consumed = &fwd_done_;
+    prev_.recvd = &recv_f_;
+    next_.produced = &fwd_done_;
+    next_.sent = &send_f_;
+    next_.consumed = &bwd_done_;
+    next_.recvd = &recv_b_;
     for (int k = 0; k < o.dp_buckets; ++k) {
       bucket_ready_.push_back(dev.create_event());
     }
     dp_done_ = dev.create_event();
     compute_->synchronize();
+  }
 
-    timers_.reset(new TimerSet(dev));
+  void declare_timers_and_stats() {
+    const auto& o = ctx_->opt;
+    timers_.reset(new TimerSet(*ctx_->dev));
     for (const char* k : {"pp_comm_time", "dp_comm_time", "pp_send_time", "pp_recv_time", "dp_exposed_time"})
       timers_->ensure(k);
     if (has_tp_) {
@@ -466,12 +500,10 @@ class Pipeline : public Strategy {
   void tp_allreduce(Stream& s, const char* timer, const char* also = nullptr) {
     int t = timers_->begin(s);
     if (sp_) {
-      int ta = timers_->begin(s);
-      tp_comm_->all_gather(tp_buf_.data(), tp_res_.data(), tp_shard_, ctx_->wire, s);
-      timers_->end(ta, s, "tp_ag_time");
-      int tr = timers_->begin(s);
-      tp_comm_->reduce_scatter(tp_res_.data(), tp_buf_.data(), tp_shard_, ctx_->wire, s);
-      timers_->end(tr, s, "tp_rs_time");
+      timed(*timers_, s, "tp_ag_time",
+            [&] { tp_comm_->all_gather(tp_buf_.data(), tp_res_.data(), tp_shard_, ctx_->wire, s); });
+      timed(*timers_, s, "tp_rs_time",
+            [&] { tp_comm_->reduce_scatter(tp_res_.data(), tp_buf_.data(), tp_shard_, ctx_->wire, s); });
     } else {
       tp_comm_->all_reduce(tp_buf_.data(), tp_res_.data(), tp_ar_, ctx_->wire, s);
     }
@@ -524,77 +556,81 @@ class Pipeline : public Strategy {
   void ep_alltoall_half(int hh) {
     const uint64_t c0 = a2a_ / 2, c = hh == 0 ? c0 : a2a_ - c0;
     const size_t off = static_cast<size_t>(hh) * c0 * E_ * es_;
-    int t = timers_->begin(*ep_stream_);
-    ep_comm_->all_to_all(ep_send_.at(off), ep_recv_.at(off), c, ctx_->wire, *ep_stream_);
-    timers_->end(t, *ep_stream_, "ep_comm_time");
+    timed(*timers_, *ep_stream_, "ep_comm_time",
+          [&] { ep_comm_->all_to_all(ep_send_.at(off), ep_recv_.at(off), c, ctx_->wire, *ep_stream_); });
+  }
+
+  // One link operation: send slot `send` and / or receive slot `recv` (-1:
+  // none), ordered by the link's events. grouped: as one group, so the two
+  // sides of a link never block each other (1F1B, interleaved: also around a
+  // single operation); GPipe issues single ungrouped calls.
+  void exchange(Link& l, int send, int recv, bool grouped) {
+    Stream& ls = *l.stream;
+    if (send >= 0) ls.wait(*(*l.produced)[send]);
+    if (recv >= 2) ls.wait(*(*l.consumed)[recv - 2]);  // recv[recv & 1] consumed
+    link_op(l, send >= 0 ? l.send[send & 1].data() : nullptr, recv >= 0 ? l.recv[recv & 1].data() : nullptr, grouped);
+    if (send >= 0) ls.record(*(*l.sent)[send]);
+    if (recv >= 0) ls.record(*(*l.recvd)[recv]);
+  }
+
+  // The timed core: pp_send_time when the operation has a send, else pp_recv_time.
+  void link_op(Link& l, const void* send, void* recv, bool grouped) {
+    const DType t = ctx_->wire;
+    Stream& ls = *l.stream;
+    timed(*timers_, ls, send ? "pp_send_time" : "pp_recv_time", [&] {
+      if (grouped) l.comm->group_start();
+      if (send) l.comm->send(send, pipe_, t, l.peer, ls);
+      if (recv) l.comm->recv(recv, pipe_, t, l.peer, ls);
+      if (grouped) l.comm->group_end();
+    });
+  }
+
+  // One compute step of a schedule on the compute stream: forward or backward
+  // of event slot `slot` (1/V of a microbatch). has_input: its input arrives
+  // over a link (the stall is the exposed pp_comm_time; a 0 is booked
+  // otherwise). wait_sent: its output buffer [slot & 1] is sent over a link, so
+  // the send two steps back must be over (a wait on an event that was never
+  // recorded - the interleaved schedule's steps without an output - is a
+  // no-op by design). The order stall, wait, compute, record is the order
+  // Device::StreamFold folds into the compute program's task gates.
+  void compute_step(bool bwd, int slot, bool has_input, bool wait_sent) {
+    const auto& recvd = bwd ? recv_b_ : recv_f_;
+    const auto& sent = bwd ? send_b_ : send_f_;
+    const double us = (bwd ? bwd_mb_us_ : fwd_mb_us_) / V_, flops = (bwd ? bwd_mb_flops_ : fwd_mb_flops_) / V_;
+    if (has_input)
+      timers_->stall_before_task(*compute_, *recvd[slot], "pp_comm_time");
+    else
+      timers_->add("pp_comm_time", 0.0);
+    if (wait_sent && slot >= 2) compute_->wait(*sent[slot - 2]);
+    // The DP buckets overlap the last backward. Only GPipe runs under
+    // --schedule reference (check_arguments), which keeps the all-reduce
+    // whole, so the one condition serves every schedule; DualPipe has one bucket.
+    const int nbk = ctx_->opt.dp_buckets;
+    if (bwd && slot == mb_ * V_ - 1 && nbk > 1 && !reference_) {
+      for (int k = 0; k < nbk; ++k) {
+        ctx_->compute->run(*compute_, us / nbk, flops / nbk);
+        compute_->record(*bucket_ready_[k]);
+        dp_stream_->wait(*bucket_ready_[k]);
+        dp_allreduce_bucket(k, nbk);
+      }
+    } else {
+      micro_compute(us, flops);
+    }
+    compute_->record(*(bwd ? bwd_done_ : fwd_done_)[slot]);
   }
 
   void enqueue_gpipe() {
-    Context& ctx = *ctx_;
-    const DType t = ctx.wire;
-    const int nbk = ctx.opt.dp_buckets;
-
-    // ---------------- forward
-    for (int i = 0; i < mb_; ++i) {
-      const int b = i & 1;
-      if (prev_) {
-        if (i >= 2) prev_stream_->wait(*fwd_done_[i - 2]);  // act_in[b] consumed
-        int tk = timers_->begin(*prev_stream_);
-        prev_->recv(act_in_[b].data(), pipe_, t, prev_peer_, *prev_stream_);
-        timers_->end(tk, *prev_stream_, "pp_recv_time");
-        prev_stream_->record(*recv_f_[i]);
-        timers_->stall_before_task(*compute_, *recv_f_[i], "pp_comm_time");
-      } else {
-        timers_->add("pp_comm_time", 0.0);
-      }
-      if (next_ && i >= 2) compute_->wait(*send_f_[i - 2]);  // act_out[b] sent
-      micro_compute(fwd_mb_us_, fwd_mb_flops_);
-      compute_->record(*fwd_done_[i]);
-      if (next_) {
-        next_stream_->wait(*fwd_done_[i]);
-        int tk = timers_->begin(*next_stream_);
-        next_->send(act_out_[b].data(), pipe_, t, next_peer_, *next_stream_);
-        timers_->end(tk, *next_stream_, "pp_send_time");
-        next_stream_->record(*send_f_[i]);
-        if (reference_) compute_->wait(*send_f_[i]);  // blocking send
-      }
+    for (int i = 0; i < mb_; ++i) {  // forward
+      if (prev_) exchange(prev_, -1, i, false);
+      compute_step(false, i, bool(prev_), bool(next_));
+      if (next_) exchange(next_, i, -1, false);
+      if (next_ && reference_) compute_->wait(*send_f_[i]);  // blocking send
     }
-    // ---------------- backward
-    for (int i = 0; i < mb_; ++i) {
-      const int b = i & 1;
-      if (next_) {
-        if (i >= 2) next_stream_->wait(*bwd_done_[i - 2]);  // grad_in[b] consumed
-        int tk = timers_->begin(*next_stream_);
-        next_->recv(grad_in_[b].data(), pipe_, t, next_peer_, *next_stream_);
-        timers_->end(tk, *next_stream_, "pp_recv_time");
-        next_stream_->record(*recv_b_[i]);
-        timers_->stall_before_task(*compute_, *recv_b_[i], "pp_comm_time");
-      } else {
-        timers_->add("pp_comm_time", 0.0);
-      }
-      if (prev_ && i >= 2) compute_->wait(*send_b_[i - 2]);
-      const bool last = i == mb_ - 1;
-      if (last && nbk > 1 && !reference_) {
-        // Overlap the DP all-reduce with the last microbatch's backward.
-        for (int k = 0; k < nbk; ++k) {
-          ctx.compute->run(*compute_, bwd_mb_us_ / nbk, bwd_mb_flops_ / nbk);
-          compute_->record(*bucket_ready_[k]);
-          dp_stream_->wait(*bucket_ready_[k]);
-          dp_allreduce_bucket(k, nbk);
-        }
-        compute_->record(*bwd_done_[i]);
-      } else {
-        micro_compute(bwd_mb_us_, bwd_mb_flops_);
-        compute_->record(*bwd_done_[i]);
-      }
-      if (prev_) {
-        prev_stream_->wait(*bwd_done_[i]);
-        int tk = timers_->begin(*prev_stream_);
-        prev_->send(grad_out_[b].data(), pipe_, t, prev_peer_, *prev_stream_);
-        timers_->end(tk, *prev_stream_, "pp_send_time");
-        prev_stream_->record(*send_b_[i]);
-        if (reference_) compute_->wait(*send_b_[i]);
-      }
+    for (int i = 0; i < mb_; ++i) {  // backward
+      if (next_) exchange(next_, -1, i, false);
+      compute_step(true, i, bool(next_), bool(prev_));
+      if (prev_) exchange(prev_, i, -1, false);
+      if (prev_ && reference_) compute_->wait(*send_b_[i]);
     }
     finish_iteration();
   }
@@ -619,10 +655,9 @@ class Pipeline : public Strategy {
         compute_->record(*inner_ready_);
         dp_stream_->wait(*inner_ready_);
       }
-      int tk = timers_->begin(es);
       void* out = ctx.opt.in_place ? grad_.data() : sum_grad_.data();
-      ep_comm_->all_reduce(grad_.data(), out, ne_, t, es);
-      const uint64_t* e = timers_->end(tk, es, "dp_ep_comm_time");
+      const uint64_t* e =
+          timed(*timers_, es, "dp_ep_comm_time", [&] { ep_comm_->all_reduce(grad_.data(), out, ne_, t, es); });
       if (&es == dp_stream_.get()) dp_end_ = e;
     }
     if (nbk == 1 || reference_) {
@@ -630,41 +665,31 @@ class Pipeline : public Strategy {
       dp_stream_->wait(*bucket_ready_[0]);
       if (mirror_comm_ && mirror_early_tick_ < 0) {
         // MoE: the whole pair gradient after the EP all-reduce
-        int tm = timers_->begin(*dp_stream_);
-        mirror_comm_->all_reduce(grad_.data(), grad_.data(), dp_ar_, t, *dp_stream_);
-        dp_end_ = timers_->end(tm, *dp_stream_, "pp_mirror_time");
+        mirror_allreduce(0, dp_ar_);
         dp_allreduce_bucket(0, 1);
       } else if (mirror_comm_) {
         // the half whose chunks finish last (model stage min(s, S-1-s)); the
         // other half was reduced mid-backward (enqueue_dualpipe)
-        const size_t half = dp_ar_ / 2;
-        void* g = static_cast<char*>(grad_.data()) + half * es_;
-        int tm = timers_->begin(*dp_stream_);
-        mirror_comm_->all_reduce(g, g, dp_ar_ - half, t, *dp_stream_);
-        timers_->end(tm, *dp_stream_, "pp_mirror_time");
+        mirror_allreduce(dp_ar_ / 2, dp_ar_ - dp_ar_ / 2);
         dp_allreduce_bucket(1, 2);
       } else {
         dp_allreduce_bucket(0, 1);
       }
     }
-    // With a compute program and nothing after it on the compute stream (no
-    // optimizer), the program's join ends the iteration once the other lanes
-    // are done, and the DP tail exposed is the DP lane's last end stamp minus
-    // the compute's last task (a gap: no wait on the compute stream);
-    // otherwise the compute stream waits for the DP lane.
-    const bool join = prog_ && !ctx.opt.optimizer && dp_end_ && timers_->task_stamps();
-    if (prog_) ctx.compute->end_program(*compute_, join);
+    join_or_stall_tail(ctx, *compute_, prog_, *dp_stream_, *dp_done_, dp_end_);
     prog_ = false;
-    if (join) {
-      timers_->stall_until(*compute_, dp_end_, "dp_exposed_time");
-    } else {
-      dp_stream_->record(*dp_done_);
-      timers_->stall_after_task(*compute_, *dp_done_, "dp_exposed_time");
-    }
     if (ctx.opt.optimizer) {
       void* g = ctx.opt.in_place ? grad_.data() : sum_grad_.data();
       optimizer_step(ctx, *compute_, params_.data(), mom_.data(), g, dp_ar_);
     }
+  }
+
+  // The DualPipe pair's sum of gradient elements [off, off + n), on the DP
+  // lane; the DP all-reduce of that range follows it there.
+  void mirror_allreduce(uint64_t off, uint64_t n) {
+    void* g = grad_.at(off * es_);
+    timed(*timers_, *dp_stream_, "pp_mirror_time",
+          [&] { mirror_comm_->all_reduce(g, g, n, ctx_->wire, *dp_stream_); });
   }
 
 
@@ -676,86 +701,27 @@ class Pipeline : public Strategy {
   // same link are posted as ONE group (send_forward_recv_backward /
   // send_backward_recv_forward), so the two sides of a link never block each
   // other; every link op waits only on events already enqueued.
-  void prev_link(int send_b, int recv_f) {
-    const DType t = ctx_->wire;
-    Stream& ls = *prev_stream_;
-    if (send_b >= 0) ls.wait(*bwd_done_[send_b]);
-    if (recv_f >= 2) ls.wait(*fwd_done_[recv_f - 2]);  // act_in[recv_f & 1] consumed
-    int tk = timers_->begin(ls);
-    prev_->group_start();
-    if (send_b >= 0) prev_->send(grad_out_[send_b & 1].data(), pipe_, t, prev_peer_, ls);
-    if (recv_f >= 0) prev_->recv(act_in_[recv_f & 1].data(), pipe_, t, prev_peer_, ls);
-    prev_->group_end();
-    timers_->end(tk, ls, send_b >= 0 ? "pp_send_time" : "pp_recv_time");
-    if (send_b >= 0) ls.record(*send_b_[send_b]);
-    if (recv_f >= 0) ls.record(*recv_f_[recv_f]);
-  }
-
-  void next_link(int send_f, int recv_b) {
-    const DType t = ctx_->wire;
-    Stream& ls = *next_stream_;
-    if (send_f >= 0) ls.wait(*fwd_done_[send_f]);
-    if (recv_b >= 2) ls.wait(*bwd_done_[recv_b - 2]);  // grad_in[recv_b & 1] consumed
-    int tk = timers_->begin(ls);
-    next_->group_start();
-    if (send_f >= 0) next_->send(act_out_[send_f & 1].data(), pipe_, t, next_peer_, ls);
-    if (recv_b >= 0) next_->recv(grad_in_[recv_b & 1].data(), pipe_, t, next_peer_, ls);
-    next_->group_end();
-    timers_->end(tk, ls, send_f >= 0 ? "pp_send_time" : "pp_recv_time");
-    if (send_f >= 0) ls.record(*send_f_[send_f]);
-    if (recv_b >= 0) ls.record(*recv_b_[recv_b]);
-  }
-
-  void fwd_step(int i) {
-    if (prev_)
-      timers_->stall_before_task(*compute_, *recv_f_[i], "pp_comm_time");
-    else
-      timers_->add("pp_comm_time", 0.0);
-    if (next_ && i >= 2) compute_->wait(*send_f_[i - 2]);  // act_out[i & 1] sent
-    micro_compute(fwd_mb_us_, fwd_mb_flops_);
-    compute_->record(*fwd_done_[i]);
-  }
-
-  void bwd_step(int j) {
-    const int nbk = ctx_->opt.dp_buckets;
-    if (next_)
-      timers_->stall_before_task(*compute_, *recv_b_[j], "pp_comm_time");
-    else
-      timers_->add("pp_comm_time", 0.0);
-    if (prev_ && j >= 2) compute_->wait(*send_b_[j - 2]);  // grad_out[j & 1] sent
-    if (j == mb_ - 1 && nbk > 1) {
-      for (int k = 0; k < nbk; ++k) {  // DP buckets overlap the last backward
-        ctx_->compute->run(*compute_, bwd_mb_us_ / nbk, bwd_mb_flops_ / nbk);
-        compute_->record(*bucket_ready_[k]);
-        dp_stream_->wait(*bucket_ready_[k]);
-        dp_allreduce_bucket(k, nbk);
-      }
-    } else {
-      micro_compute(bwd_mb_us_, bwd_mb_flops_);
-    }
-    compute_->record(*bwd_done_[j]);
-  }
-
   void enqueue_1f1b() {
     const int w = std::min(S_ - stage_ - 1, mb_);
     const int steady = mb_ - w;
+    const bool up = bool(prev_), down = bool(next_);
     for (int i = 0; i < w; ++i) {
-      if (prev_) prev_link(-1, i);
-      fwd_step(i);
-      if (next_) next_link(i, -1);
+      if (up) exchange(prev_, -1, i, true);
+      compute_step(false, i, up, down);
+      if (down) exchange(next_, i, -1, true);
     }
-    if (steady > 0 && prev_) prev_link(-1, w);
+    if (steady > 0 && up) exchange(prev_, -1, w, true);
     for (int j = 0; j < steady; ++j) {
       const int i = w + j;
-      fwd_step(i);
-      if (next_) next_link(i, j);  // send F(i) + receive B(j)
-      bwd_step(j);
-      if (prev_) prev_link(j, j + 1 < steady ? i + 1 : -1);  // send B(j) (+ receive F(i+1))
+      compute_step(false, i, up, down);
+      if (down) exchange(next_, i, j, true);  // send F(i) + receive B(j)
+      compute_step(true, j, down, up);
+      if (up) exchange(prev_, j, j + 1 < steady ? i + 1 : -1, true);  // send B(j) (+ receive F(i+1))
     }
     for (int j = steady; j < mb_; ++j) {
-      if (next_) next_link(-1, j);
-      bwd_step(j);
-      if (prev_) prev_link(j, -1);
+      if (down) exchange(next_, -1, j, true);
+      compute_step(true, j, down, up);
+      if (up) exchange(prev_, j, -1, true);
     }
     finish_iteration();
   }
@@ -778,37 +744,6 @@ class Pipeline : public Strategy {
   bool in_b(int k) const { return !(stage_ == S_ - 1 && chunk_b(k) == V_ - 1); }
   bool out_b(int k) const { return !(stage_ == 0 && chunk_b(k) == 0); }
 
-  void fwd_chunk(int k) {
-    if (S_ > 1 && in_f(k))
-      timers_->stall_before_task(*compute_, *recv_f_[k], "pp_comm_time");
-    else
-      timers_->add("pp_comm_time", 0.0);
-    if (S_ > 1 && k >= 2) compute_->wait(*send_f_[k - 2]);  // act_out[k & 1] sent (no-op if never recorded)
-    micro_compute(fwd_mb_us_ / V_, fwd_mb_flops_ / V_);
-    compute_->record(*fwd_done_[k]);
-  }
-
-  void bwd_chunk(int j) {
-    const int nbk = ctx_->opt.dp_buckets;
-    const int total = mb_ * V_;
-    if (S_ > 1 && in_b(j))
-      timers_->stall_before_task(*compute_, *recv_b_[j], "pp_comm_time");
-    else
-      timers_->add("pp_comm_time", 0.0);
-    if (S_ > 1 && j >= 2) compute_->wait(*send_b_[j - 2]);  // grad_out[j & 1] sent
-    if (j == total - 1 && nbk > 1) {
-      for (int k = 0; k < nbk; ++k) {  // DP buckets overlap the last backward
-        ctx_->compute->run(*compute_, bwd_mb_us_ / V_ / nbk, bwd_mb_flops_ / V_ / nbk);
-        compute_->record(*bucket_ready_[k]);
-        dp_stream_->wait(*bucket_ready_[k]);
-        dp_allreduce_bucket(k, nbk);
-      }
-    } else {
-      micro_compute(bwd_mb_us_ / V_, bwd_mb_flops_ / V_);
-    }
-    compute_->record(*bwd_done_[j]);
-  }
-
   // Link groups of one step (-1 = nothing in that slot).
   void links(int send_f, int recv_b, int send_b, int recv_f) {
     if (S_ == 1) return;
@@ -817,10 +752,15 @@ class Pipeline : public Strategy {
     // has no cycle of stages each waiting on its successor. Stream-ordered
     // backends are indifferent to the order (two independent streams).
     const bool prev_first = interleaved_ && stage_ == 0;
-    if (prev_first && (send_b >= 0 || recv_f >= 0)) prev_link(send_b, recv_f);
-    if (send_f >= 0 || recv_b >= 0) next_link(send_f, recv_b);
-    if (!prev_first && (send_b >= 0 || recv_f >= 0)) prev_link(send_b, recv_f);
+    if (prev_first && (send_b >= 0 || recv_f >= 0)) exchange(prev_, send_b, recv_f, true);
+    if (send_f >= 0 || recv_b >= 0) exchange(next_, send_f, recv_b, true);
+    if (!prev_first && (send_b >= 0 || recv_f >= 0)) exchange(prev_, send_b, recv_f, true);
   }
+
+  // Step k of the interleaved order: chunk chunk_f(k) / chunk_b(k); the first
+  // chunk's forward on stage 0 and the last chunk's backward on the last stage
+  // have no input.
+  void chunk_step(bool bwd, int k) { compute_step(bwd, k, S_ > 1 && (bwd ? in_b(k) : in_f(k)), S_ > 1); }
 
   void enqueue_interleaved() {
     const int total = mb_ * V_;
@@ -828,22 +768,22 @@ class Pipeline : public Strategy {
     const int rem = total - w;
     links(-1, -1, -1, in_f(0) ? 0 : -1);
     for (int k = 0; k < w; ++k) {
-      fwd_chunk(k);
+      chunk_step(false, k);
       const int rf = k + 1 < total && in_f(k + 1) ? k + 1 : -1;
       const int rb = k == w - 1 && rem > 0 && in_b(0) ? 0 : -1;
       links(out_f(k) ? k : -1, rb, -1, rf);
     }
     for (int j = 0; j < rem; ++j) {
       const int k = w + j;
-      fwd_chunk(k);
-      bwd_chunk(j);
+      chunk_step(false, k);
+      chunk_step(true, j);
       const int rf = k + 1 < total && in_f(k + 1) ? k + 1 : -1;
       const int rb = j + 1 < total && in_b(j + 1) ? j + 1 : -1;
       links(out_f(k) ? k : -1, rb, out_b(j) ? j : -1, rf);
     }
     if (rem == 0) links(-1, in_b(0) ? 0 : -1, -1, -1);
     for (int j = rem; j < total; ++j) {
-      bwd_chunk(j);
+      chunk_step(true, j);
       const int rb = j + 1 < total && in_b(j + 1) ? j + 1 : -1;
       links(-1, rb, out_b(j) ? j : -1, -1);
     }
@@ -984,11 +924,12 @@ class Pipeline : public Strategy {
 
   // One link's group at a tick boundary: what this rank's op of the tick
   // sends over it, and what the neighbour's op of the tick sends to us.
+  // Unlike exchange(): every slot has a receive buffer of its own, the send
+  // goes out of buffer 0 and nothing waits for a buffer's reuse.
   void dualpipe_link(bool next, const DpOp& mine, const DpOp& theirs) {
-    Communicator* c = next ? next_.get() : prev_.get();
-    if (!c) return;
-    Stream& ls = next ? *next_stream_ : *prev_stream_;
-    const int peer = next ? next_peer_ : prev_peer_;
+    Link& l = next ? next_ : prev_;
+    if (!l) return;
+    Stream& ls = *l.stream;
     // our output travels towards `next` for down-forwards and up-backwards
     const bool send = mine.dir >= 0 && ((mine.dir == 0) != mine.bwd) == next &&
                       (mine.bwd ? dp_pos(stage_, mine.dir) > 0 : dp_pos(stage_, mine.dir) < S_ - 1);
@@ -996,15 +937,10 @@ class Pipeline : public Strategy {
     const bool recv = theirs.dir >= 0 && ((theirs.dir == 0) != theirs.bwd) == !next &&
                       (theirs.bwd ? dp_pos(nstage, theirs.dir) > 0 : dp_pos(nstage, theirs.dir) < S_ - 1);
     if (!send && !recv) return;
-    const DType t = ctx_->wire;
     if (send) ls.wait(mine.bwd ? *bwd_done_[dp_slot(mine.dir, mine.mb)] : *fwd_done_[dp_slot(mine.dir, mine.mb)]);
-    int tk = timers_->begin(ls);
-    c->group_start();
-    if (send) c->send(next ? act_out_[0].data() : grad_out_[0].data(), pipe_, t, peer, ls);
     const int slot = recv ? dp_slot(theirs.dir, theirs.mb) : 0;
-    if (recv) c->recv(dpbuf_[static_cast<size_t>(theirs.bwd ? mb_ + slot : slot)].data(), pipe_, t, peer, ls);
-    c->group_end();
-    timers_->end(tk, ls, send ? "pp_send_time" : "pp_recv_time");
+    link_op(l, send ? l.send[0].data() : nullptr,
+            recv ? dpbuf_[static_cast<size_t>(theirs.bwd ? mb_ + slot : slot)].data() : nullptr, true);
     if (recv) ls.record(theirs.bwd ? *recv_b_[slot] : *recv_f_[slot]);
   }
 
@@ -1013,32 +949,16 @@ class Pipeline : public Strategy {
     for (const auto& row : dp_ticks_) {
       const DpOp& op = row[static_cast<size_t>(stage_)];
       if (op.dir >= 0) {
-        const int slot = dp_slot(op.dir, op.mb);
-        if (!op.bwd) {
-          if (dp_pos(stage_, op.dir) > 0)
-            timers_->stall_before_task(*compute_, *recv_f_[slot], "pp_comm_time");
-          else
-            timers_->add("pp_comm_time", 0.0);
-          micro_compute(fwd_mb_us_, fwd_mb_flops_);
-          compute_->record(*fwd_done_[slot]);
-        } else {
-          if (dp_pos(stage_, op.dir) < S_ - 1)
-            timers_->stall_before_task(*compute_, *recv_b_[slot], "pp_comm_time");
-          else
-            timers_->add("pp_comm_time", 0.0);
-          micro_compute(bwd_mb_us_, bwd_mb_flops_);
-          compute_->record(*bwd_done_[slot]);
-        }
+        // a copy's first stage forwards, and its last stage backwards, without an input
+        const int pos = dp_pos(stage_, op.dir);
+        compute_step(op.bwd, dp_slot(op.dir, op.mb), op.bwd ? pos < S_ - 1 : pos > 0, false);
       }
       if (next_) dualpipe_link(true, op, row[static_cast<size_t>(stage_ + 1)]);
       if (prev_) dualpipe_link(false, op, row[static_cast<size_t>(stage_ - 1)]);
       if (tick == mirror_early_tick_) {
         compute_->record(*mirror_ready_);
         dp_stream_->wait(*mirror_ready_);
-        void* g = grad_.data();
-        int tm = timers_->begin(*dp_stream_);
-        mirror_comm_->all_reduce(g, g, dp_ar_ / 2, ctx_->wire, *dp_stream_);
-        timers_->end(tm, *dp_stream_, "pp_mirror_time");
+        mirror_allreduce(0, dp_ar_ / 2);
         dp_allreduce_bucket(0, 2);  // and that half's DP all-reduce right behind it
       }
       ++tick;
@@ -1076,9 +996,8 @@ class Pipeline : public Strategy {
     const uint64_t n = base + (static_cast<uint64_t>(k) < rem ? 1 : 0);
     void* in = grad_.at(off * es_);
     void* out = ctx_->opt.in_place ? in : sum_grad_.at(off * es_);
-    int tk = timers_->begin(*dp_stream_);
-    dp_comm_->all_reduce(in, out, n, ctx_->wire, *dp_stream_);
-    dp_end_ = timers_->end(tk, *dp_stream_, "dp_comm_time");
+    dp_end_ = timed(*timers_, *dp_stream_, "dp_comm_time",
+                    [&] { dp_comm_->all_reduce(in, out, n, ctx_->wire, *dp_stream_); });
   }
 
   // Whether the compute lane may be one compute program: not with TP or EP
@@ -1105,8 +1024,8 @@ class Pipeline : public Strategy {
 
   std::vector<Stream*> streams() override {
     std::vector<Stream*> ss = {compute_.get(), dp_stream_.get()};
-    if (prev_) ss.push_back(prev_stream_.get());
-    if (next_) ss.push_back(next_stream_.get());
+    if (prev_) ss.push_back(prev_.stream.get());
+    if (next_) ss.push_back(next_.stream.get());
     return ss;
   }
   bool capturable() const override { return !reference_; }
@@ -1116,20 +1035,13 @@ class Pipeline : public Strategy {
   bool lanes_without_program() const override { return !dualpipe_; }
 
   void synchronize() override {
-    std::vector<Stream*> ss = {compute_.get(), dp_stream_.get()};
     std::vector<Communicator*> cs = {dp_comm_.get()};
-    if (prev_) {
-      ss.push_back(prev_stream_.get());
-      cs.push_back(prev_.get());
-    }
-    if (next_) {
-      ss.push_back(next_stream_.get());
-      cs.push_back(next_.get());
-    }
+    if (prev_) cs.push_back(prev_.comm.get());
+    if (next_) cs.push_back(next_.comm.get());
     if (tp_comm_) cs.push_back(tp_comm_.get());
     if (ep_comm_) cs.push_back(ep_comm_.get());
     if (mirror_comm_) cs.push_back(mirror_comm_.get());
-    sync_streams(ss, cs, *ctx_->dev);
+    sync_streams(streams(), cs, *ctx_->dev);
     timers_->resolve();
   }
 
@@ -1261,10 +1173,9 @@ class Pipeline : public Strategy {
   uint64_t spmb_ = 0, pipe_ = 0, dp_ar_ = 0, tp_ar_ = 0, ne_ = 0, a2a_ = 0;
   size_t es_ = 2;
   double fwd_mb_us_ = 0, bwd_mb_us_ = 0, fwd_mb_flops_ = 0, bwd_mb_flops_ = 0;
-  std::unique_ptr<Communicator> prev_, next_, tp_comm_, ep_comm_, dp_comm_;
-  int prev_peer_ = 0, next_peer_ = 1;
-  std::unique_ptr<Stream> compute_, prev_stream_, next_stream_, dp_stream_;
-  Buffer act_in_[2], act_out_[2], grad_in_[2], grad_out_[2];
+  Link prev_, next_;  // to stage - 1 (sends gradients, receives activations) and to stage + 1 (the reverse)
+  std::unique_ptr<Communicator> tp_comm_, ep_comm_, dp_comm_;
+  std::unique_ptr<Stream> compute_, dp_stream_;
   Buffer grad_, sum_grad_, tp_buf_, tp_res_, ep_send_, ep_recv_, params_, mom_;
   std::vector<std::unique_ptr<Event>> recv_f_, fwd_done_, send_f_, recv_b_, bwd_done_, send_b_, bucket_ready_;
   std::unique_ptr<Event> dp_done_;
