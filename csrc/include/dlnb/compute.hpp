@@ -23,6 +23,13 @@
 //           compute program): it stamps its own start and end;
 //   flops - the same with the table's FLOP count as the work (MI355X-native
 //           compute time).
+//   hbm   - memory-bound compute (norms, activations, the optimizer): one block
+//           per CU streams c = a + b over three bf16 arrays far larger than
+//           the Infinity Cache until the table's deadline, on the same CU
+//           budget as gemm, and counts the bytes it moved; the report's
+//           compute.hbm.GBps beside collectives against the same run alone is
+//           an HBM-contention reading that needs no calibration. One kernel
+//           per task like spin (no gates, no programs); sleep on the CPU device.
 #pragma once
 
 #include <memory>
@@ -35,7 +42,7 @@
 
 namespace dlnb {
 
-enum class ComputeMode { Sleep, Spin, Gemm, GemmWork, Flops };
+enum class ComputeMode { Sleep, Spin, Gemm, GemmWork, Flops, Hbm };
 
 ComputeMode parse_compute_mode(const std::string& s, DeviceKind dev);
 const char* compute_mode_name(ComputeMode m);

@@ -9,6 +9,8 @@
 //                          (the device-side equivalent of the reference's
 //                          usleep: the GPU is idle, the stream is busy)
 //   * busy_spin         - every CU runs dependent FMAs until a deadline
+//   * hbm_stream        - one block per CU streams c = a + b (bf16) through
+//                          HBM, once or until a deadline, and counts its bytes
 //   * gemm_tn           - C[M,N] (bf16) = A[M,K] · B[N,K]^T, MFMA 16x16x32
 //                          bf16 or OCP-fp8 e4m3 operands, 256x256 tiles,
 //                          global_load_lds staging into an XOR-swizzled LDS
@@ -131,6 +133,22 @@ bool queues_independent(void* a, void* b, uint64_t timeout_ticks);
 // there (s_memrealtime), so stall timers work from the task itself (gap()).
 void idle_wait(uint64_t ticks, void* stream, uint64_t* start = nullptr, uint64_t* start2 = nullptr);
 void busy_spin(uint64_t ticks, int blocks, void* stream, uint64_t* start = nullptr, uint64_t* start2 = nullptr);
+// HBM streaming (hbm_stream.hip): c[i] = bf16(float(a[i]) + float(b[i])) over
+// three bf16 arrays of n elements (n % 8 == 0, 16-byte aligned pointers) by a
+// persistent grid of `grid` 1024-thread blocks, one per CU (0: every CU; at
+// most the CUs). The work unit is a chunk of kHbmChunkBytes per array (the
+// last one may be short); block blk takes chunks blk, blk + grid, ...
+//   ticks == 0: one shot, every chunk exactly once.
+//   ticks > 0: the sequence wraps round the arrays; a block reads the clock
+//     once per chunk and leaves after the chunk in hand once `ticks` have
+//     passed since it entered the kernel. start / start2 as busy_spin's.
+// Accounting (optional; device memory the kernel adds to, so replays of a
+// captured launch accumulate): totals[0] += chunks processed by the grid,
+// totals[1] += ticks (once per launch); per_block[blk] = the block's count.
+constexpr size_t kHbmChunkBytes = 64 * 1024;
+void hbm_stream(const void* a, const void* b, void* c, size_t n, uint64_t ticks, int grid, void* stream,
+                uint64_t* start = nullptr, uint64_t* start2 = nullptr, uint64_t* totals = nullptr /* {chunks, ticks} */,
+                uint64_t* per_block = nullptr);
 // The deadline clock's rate in Hz: measured against the host's steady clock
 // once per process (clock_cal_begin starts the window - the GPU device does
 // at creation - and the first wallclock_hz call ends it, sleeping until

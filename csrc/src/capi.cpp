@@ -236,6 +236,24 @@ int dlnb_busy_spin_us(double us, int device, void* stream) {
   });
 }
 
+// c = a + b over n bf16 elements with the HBM-streaming kernel
+// (kernels::hbm_stream): us = 0 sweeps the arrays once, us > 0 keeps sweeping
+// for that long. grid 0 = every CU. start (host-mapped or device memory),
+// totals (two device words {chunks, ticks} the kernel adds to) and per_block
+// (grid device words) are optional.
+int dlnb_hbm_stream(const void* a, const void* b, void* c, size_t n, double us, int device, int grid, void* stream,
+                    void* start, void* totals, void* per_block) {
+  return guard([&] {
+    DLNB_REQUIRE(us >= 0, "dlnb_hbm_stream: negative duration");
+    uint64_t ticks = 0;
+    if (us > 0) ticks = std::max<uint64_t>(1, static_cast<uint64_t>(us * 1e-6 * dlnb::kernels::wallclock_hz(device) + 0.5));
+    dlnb::kernels::hbm_stream(a, b, c, n, ticks, grid, stream, static_cast<uint64_t*>(start), nullptr,
+                              static_cast<uint64_t*>(totals), static_cast<uint64_t*>(per_block));
+  });
+}
+
+size_t dlnb_hbm_chunk_bytes() { return dlnb::kernels::kHbmChunkBytes; }
+
 int dlnb_sgd_momentum_bf16(void* p, void* m, const void* g, size_t n, float lr, float beta, void* stream) {
   return guard([&] { dlnb::kernels::sgd_momentum_bf16(p, m, g, n, lr, beta, stream); });
 }

@@ -18,7 +18,8 @@ ComputeMode parse_compute_mode(const std::string& s, DeviceKind dev) {
   if (s == "gemm") return ComputeMode::Gemm;
   if (s == "gemm-work" || s == "gemm_work") return ComputeMode::GemmWork;
   if (s == "flops") return ComputeMode::Flops;
-  DLNB_THROW("unknown compute mode '" << s << "' (auto, sleep, spin, gemm, flops)");
+  if (s == "hbm") return ComputeMode::Hbm;
+  DLNB_THROW("unknown compute mode '" << s << "' (auto, sleep, spin, gemm, gemm-work, flops, hbm)");
 }
 
 const char* compute_mode_name(ComputeMode m) {
@@ -28,6 +29,7 @@ const char* compute_mode_name(ComputeMode m) {
     case ComputeMode::Gemm: return "gemm";
     case ComputeMode::GemmWork: return "gemm-work";
     case ComputeMode::Flops: return "flops";
+    case ComputeMode::Hbm: return "hbm";
   }
   return "?";
 }
@@ -49,7 +51,7 @@ class CpuCompute : public ComputeEngine {
         while (now_s() < end) x = x * 1.0000001 + 1e-9;
       });
     } else {
-      // sleep; gemm/flops have no CPU implementation and fall back to sleep.
+      // sleep; gemm/flops/hbm have no CPU implementation and fall back to sleep.
       dev_.host_task(s, [d] { precise_sleep_us(d); });
     }
   }
@@ -112,7 +114,7 @@ class GpuCompute : public ComputeEngine {
     // rank's share of free memory (ranks sharing the GPU each allocate their
     // own set). Large-FFN models (K = ffn up to 64 Ki) shrink K, keeping its
     // multiple (ffn 53248 x hidden 16384 is ~2.6 GB per rank).
-    if (mode_ != ComputeMode::Sleep && mode_ != ComputeMode::Spin) {
+    if (gemm_mode()) {
       const size_t esz = dtype_size(dtype_);
       const double share = static_cast<double>(dev_.free_memory()) / std::max(1, shape.ranks_on_device) / 8.0;
       auto bytes = [&](int k) {
@@ -121,7 +123,35 @@ class GpuCompute : public ComputeEngine {
       while (K_ > 512 && share > 0 && bytes(K_) > share) K_ = std::max(512, (K_ / 2 + kmul - 1) / kmul * kmul);
     }
     // GEMM operands for every GEMM mode
-    if (mode_ != ComputeMode::Sleep && mode_ != ComputeMode::Spin) alloc_operands();
+    if (gemm_mode()) alloc_operands();
+    if (mode_ == ComputeMode::Hbm) {
+      // Three bf16 arrays of 512 MiB: each alone is twice the 256 MiB Infinity
+      // Cache, so the sweep cannot live in cache. Halved while the set exceeds
+      // 1/8 of this rank's share of free memory (the GEMM operands' rule);
+      // always a whole number of chunks. The grid leaves comm_cus CUs free
+      // (one block per CU, hbm_stream.hip), as the GEMM's does.
+      hbm_bytes_ = size_t(512) << 20;
+      const double share = static_cast<double>(dev_.free_memory()) / std::max(1, shape.ranks_on_device) / 8.0;
+      while (hbm_bytes_ > kernels::kHbmChunkBytes && share > 0 && 3.0 * static_cast<double>(hbm_bytes_) > share)
+        hbm_bytes_ /= 2;
+      grid_ = std::max(1, cus_ - std::max(0, shape.comm_cus));
+      // Ranks sharing the device split those CUs: a block that found no CU
+      // until another rank's task ended would run its whole deadline from
+      // there, and the task would last up to twice the table's time.
+      grid_ = std::max(1, grid_ / std::max(1, shape.ranks_on_device));
+      A_ = dev_.alloc(hbm_bytes_);
+      B_ = dev_.alloc(hbm_bytes_);
+      C_ = dev_.alloc(hbm_bytes_);
+      hbm_totals_ = dev_.alloc(2 * sizeof(uint64_t));
+      auto s = dev_.create_stream(false);
+      dev_.fill_random(A_.data(), hbm_bytes_ / 2, DType::BF16, 1, *s);
+      dev_.fill_random(B_.data(), hbm_bytes_ / 2, DType::BF16, 2, *s);
+      dev_.memset_async(hbm_totals_.data(), 0, 2 * sizeof(uint64_t), *s);
+      // the kernel's first launch (code object load, the one-block-per-CU
+      // check) here, never inside a graph capture: one chunk, counted nowhere
+      kernels::hbm_stream(A_.data(), B_.data(), C_.data(), kernels::kHbmChunkBytes / 2, 0, 1, s->native());
+      s->synchronize();
+    }
     if (mode_ == ComputeMode::Gemm || fixed_) {
       // one 64-byte line per compute stream; the counters (DlCounter)
       slots_ = dev_.alloc(kSlots * 64);
@@ -417,7 +447,7 @@ class GpuCompute : public ComputeEngine {
       flush_program(s);
     }
     if (mode_ == ComputeMode::Gemm) chain_live_[slot_for(s)] = false;  // a chain restarts at every unchained task
-    if (mode_ == ComputeMode::Sleep || mode_ == ComputeMode::Spin) {
+    if (mode_ == ComputeMode::Sleep || mode_ == ComputeMode::Spin || mode_ == ComputeMode::Hbm) {
       // the kernel stamps its own start (stall timers: gap() from it)
       uint64_t* extra = extra_start_;
       extra_start_ = nullptr;
@@ -426,8 +456,11 @@ class GpuCompute : public ComputeEngine {
         if (extra) dev_.stamp(s, extra);
       } else if (mode_ == ComputeMode::Sleep) {
         kernels::idle_wait(ticks(d), s.native(), start, extra);
-      } else {
+      } else if (mode_ == ComputeMode::Spin) {
         kernels::busy_spin(ticks(d), cus_, s.native(), start, extra);
+      } else {
+        kernels::hbm_stream(A_.data(), B_.data(), C_.data(), hbm_bytes_ / 2, std::max<uint64_t>(ticks(d), 1), grid_,
+                            s.native(), start, extra, hbm_totals_.as<uint64_t>(), nullptr);
       }
       return;
     }
@@ -484,7 +517,25 @@ class GpuCompute : public ComputeEngine {
       j["programs"] = programs_launched_;
       j["program_tasks"] = program_tasks_;
     }
-    if (A_.data()) {
+    if (mode_ == ComputeMode::Hbm) {
+      // what the streaming tasks moved so far (device totals: every launch and
+      // every replay of a captured one adds to them) in the time they ran
+      uint64_t v[2] = {0, 0};
+      auto st = dev_.create_stream(false);
+      dev_.copy_async(v, hbm_totals_.data(), sizeof(v), *st);
+      st->synchronize();
+      Json h = Json::object();
+      h["working_set_bytes"] = static_cast<double>(3 * hbm_bytes_);
+      h["chunk_bytes"] = static_cast<double>(kernels::kHbmChunkBytes);
+      h["grid"] = grid_;
+      const double bytes = 3.0 * static_cast<double>(kernels::kHbmChunkBytes) * static_cast<double>(v[0]);
+      const double busy = static_cast<double>(v[1]) / hz();
+      h["bytes_moved"] = bytes;
+      h["busy_s"] = busy;
+      h["GBps"] = busy > 0 ? bytes / busy / 1e9 : 0.0;
+      j["hbm"] = h;
+    }
+    if (gemm_mode()) {
       j["gemm_dtype"] = dtype_name(dtype_);
       j["gemm_N"] = N_;
       j["gemm_K"] = K_;
@@ -506,7 +557,7 @@ class GpuCompute : public ComputeEngine {
   }
   ComputeMode mode() const override { return mode_; }
   bool product(const void** c, size_t* count, DType* t) const override {
-    if (!C_.data()) return false;
+    if (!gemm_mode()) return false;
     *c = C_.data();
     *count = static_cast<size_t>(kMmax) * N_;
     *t = DType::BF16;
@@ -514,6 +565,7 @@ class GpuCompute : public ComputeEngine {
   }
 
  private:
+  bool gemm_mode() const { return mode_ == ComputeMode::Gemm || fixed_; }
   uint64_t ticks(double us) const { return static_cast<uint64_t>(us * 1e-6 * hz() + 0.5); }
   double hz() const {
     if (hz_ <= 0.0) hz_ = kernels::wallclock_hz(dev_.index());
@@ -952,7 +1004,9 @@ class GpuCompute : public ComputeEngine {
   uint32_t tail_mul_ = 2;      // the tail's K-tile multiple
   FixedCal cal_;
   bool cal_given_ = false;
-  Buffer A_, B_, C_;
+  Buffer A_, B_, C_;  // GEMM operands and product; hbm: the three streamed arrays
+  size_t hbm_bytes_ = 0;  // hbm: bytes per array (a whole number of chunks)
+  Buffer hbm_totals_;     // hbm: {chunks, ticks} the kernels add to (kernels::hbm_stream)
   TimerSet* task_timers_ = nullptr;
 };
 

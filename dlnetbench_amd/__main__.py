@@ -5,7 +5,7 @@
     commtest [-n N] <args...>
                       exact check / bandwidth sweep of a comm backend (dlnb commtest)
     launch -n N <program ...>   generic N-rank launcher (utils/launch.py)
-    sweep | plots | report | plan | schedule-sim | roofline | measure | gemm-bench | clock-check |
+    sweep | plots | report | plan | schedule-sim | roofline | measure | gemm-bench | hbm-bench | clock-check |
     prof-summary | bench-report | download-models | timeline | interference
                       the tools, each with its own --help
 
@@ -32,6 +32,7 @@ TOOLS = {
     "roofline": "dlnetbench_amd.models.roofline",
     "measure": "dlnetbench_amd.models.measure",
     "gemm-bench": "dlnetbench_amd.tools.gemm_bench",
+    "hbm-bench": "dlnetbench_amd.tools.hbm_bench",
     "clock-check": "dlnetbench_amd.tools.clock_check",
     "prof-summary": "dlnetbench_amd.tools.prof_summary",
     "bench-report": "dlnetbench_amd.tools.bench_report",

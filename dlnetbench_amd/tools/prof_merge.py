@@ -47,6 +47,7 @@ MAX_CLOCK_GHZ = 2.5
 # first match wins
 CLASSES = [
     ("compute_gemm", re.compile(r"gemm", re.I)),
+    ("compute_hbm", re.compile(r"hbm_stream", re.I)),
     ("compute_wait", re.compile(r"idle_wait|busy_spin|spin_kernel|sleep", re.I)),
     ("rccl", re.compile(r"nccl|rccl(?!r)", re.I)),
     ("xgmi", re.compile(r"xgmi::|ag_kernel|rs_kernel|ar1_kernel|ar2_kernel|a2a_kernel|send_kernel|recv_kernel|"
