@@ -17,7 +17,7 @@ OPT     ?= -O3
 CXXFLAGS = $(OPT) -std=c++17 -fPIC -Wall -Wno-unused-result -Icsrc/include --offload-arch=$(ARCH)
 LDLIBS   = -L$(ROCM)/lib -lrccl -lamdhip64 -lpthread -lrt -Wl,-rpath,$(ROCM)/lib
 
-# every kernel file (kernels, gemm_*, xgmi, hbm_stream) and runtime source: the asan / tsan trees take the same list
+# every kernel file (kernels, gemm_*, xgmi, hbm_stream, wire_quant) and runtime source: the asan / tsan trees take the same list
 LIB_SRCS := $(wildcard csrc/src/*.cpp) $(wildcard csrc/kernels/*.hip)
 # host-only C++ (no device pass): the CPU backend's multiversioned SIMD loops
 HOST_SRCS := $(wildcard csrc/host/*.cpp)

@@ -126,6 +126,27 @@ std::unique_ptr<CommFactory> make_loopback_factory(HostGroup& world, Device& dev
 // otherwise returns inner. Tests of the exactness checks only.
 std::unique_ptr<CommFactory> wrap_comm_faults(std::unique_ptr<CommFactory> inner, Device& dev, int world_rank);
 
+// --wire-quant: what a rank's quantizing communicators handed to their inner
+// transports, per collective kind (indexed by CollKind, all-reduce to
+// all-to-all). payload_bytes: the bf16 bytes (2 per element) of everything
+// that went out in quantized form - a reduce-scatter's W blocks, an
+// all-reduce's W chunks plus the reduced chunk it gathers; wire_bytes: the
+// bytes of their wire blocks. Counted when an operation is enqueued (an
+// operation captured into a graph counts once, not per replay).
+struct WireQuantCounts {
+  struct Op {
+    uint64_t calls = 0, payload_bytes = 0, wire_bytes = 0;
+  };
+  Op ops[4];
+};
+// mode "mxfp8": wraps every communicator of `inner` in the quantized wire
+// (comm_quant.cpp: bf16 collectives of groups of more than one rank travel as
+// MXFP8 wire blocks, dlnb/wire_quant.hpp); "none": returns inner. Wraps the
+// raw backend, below wrap_comm_faults and the comm log, so fault injection
+// and timeline spans see the bf16 operation, conversions included.
+std::unique_ptr<CommFactory> wrap_comm_quant(std::unique_ptr<CommFactory> inner, Device& dev, const std::string& mode,
+                                             WireQuantCounts* counts = nullptr);
+
 // Host-memory helpers of the CPU backends (multi-threaded for large sizes).
 // dst[i] = sum over srcs of src[i] (fp32 accumulation); dst may alias a src.
 void host_reduce_sum(DType t, void* dst, const std::vector<const char*>& srcs, size_t count);

@@ -51,6 +51,9 @@ struct Options {
   int ranks = 2;                  // loopback: in-process ranks (threads) sharing one device
   std::string compute = "auto";   // auto | sleep | spin | gemm | flops
   std::string wire_dtype = "bf16";
+  // none | mxfp8: bf16 collectives travel as MXFP8 wire blocks, quantized and
+  // dequantized around the transport (comm_quant.cpp); needs --wire-dtype bf16
+  std::string wire_quant = "none";
   std::string compute_dtype = "auto";  // auto (from stats Dtype) | bf16 | fp8
   std::string schedule = "overlap";    // overlap | reference
   std::string tp_granularity = "microbatch";  // microbatch | layer

@@ -40,6 +40,8 @@ struct Context {
   std::unique_ptr<Device> dev;
   std::unique_ptr<CommFactory> comms;
   std::vector<CommRecord> comm_log;
+  // --wire-quant: what this rank's communicators quantized (report block wire_quant)
+  WireQuantCounts wire_quant;
   // every communicator the strategy created (outermost wrapper; owned by the
   // strategy): the failure path aborts them all (device_failure)
   std::vector<Communicator*> live_comms;

@@ -11,6 +11,7 @@
 #include "dlnb/compute.hpp"
 #include "dlnb/kernels.hpp"
 #include "dlnb/strategy.hpp"
+#include "dlnb/wire_quant.hpp"
 #include "dlnb/workload.hpp"
 
 namespace {
@@ -256,6 +257,40 @@ size_t dlnb_hbm_chunk_bytes() { return dlnb::kernels::kHbmChunkBytes; }
 
 int dlnb_sgd_momentum_bf16(void* p, void* m, const void* g, size_t n, float lr, float beta, void* stream) {
   return guard([&] { dlnb::kernels::sgd_momentum_bf16(p, m, g, n, lr, beta, stream); });
+}
+
+// MXFP8 wire format of bf16 messages (dlnb/wire_quant.hpp): the kernels on a
+// stream, and the host implementations (no GPU needed).
+size_t dlnb_mx_wire_bytes(size_t n) { return dlnb::mx_wire_bytes(n); }
+
+int dlnb_mx_quantize(const void* src, size_t n_total, size_t block_elems, size_t nblocks, void* wire, void* stream) {
+  return guard([&] { dlnb::kernels::mx_quantize(src, n_total, block_elems, nblocks, wire, stream); });
+}
+
+int dlnb_mx_dequantize(const void* wire, size_t block_elems, size_t nblocks, void* dst, size_t n_total, void* stream) {
+  return guard([&] { dlnb::kernels::mx_dequantize(wire, block_elems, nblocks, dst, n_total, stream); });
+}
+
+int dlnb_mx_dequant_reduce(const void* wire, size_t block_elems, size_t nblocks, void* dst, size_t n, void* stream) {
+  return guard([&] { dlnb::kernels::mx_dequant_reduce(wire, block_elems, nblocks, dst, n, stream); });
+}
+
+int dlnb_mx_quantize_host(const void* src, size_t n_total, size_t block_elems, size_t nblocks, void* wire) {
+  return guard([&] {
+    dlnb::mx_quantize_host(static_cast<const uint16_t*>(src), n_total, block_elems, nblocks, static_cast<uint8_t*>(wire));
+  });
+}
+
+int dlnb_mx_dequantize_host(const void* wire, size_t block_elems, size_t nblocks, void* dst, size_t n_total) {
+  return guard([&] {
+    dlnb::mx_dequantize_host(static_cast<const uint8_t*>(wire), block_elems, nblocks, static_cast<uint16_t*>(dst), n_total);
+  });
+}
+
+int dlnb_mx_dequant_reduce_host(const void* wire, size_t block_elems, size_t nblocks, void* dst, size_t n) {
+  return guard([&] {
+    dlnb::mx_dequant_reduce_host(static_cast<const uint8_t*>(wire), block_elems, nblocks, static_cast<uint16_t*>(dst), n);
+  });
 }
 
 double dlnb_wallclock_hz(int device) { return dlnb::kernels::wallclock_hz(device); }

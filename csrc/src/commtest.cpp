@@ -20,6 +20,12 @@
 // uploaded between replays (each replay must see fresh sequence numbers);
 // bench mode captures the timed loop of one op and replays it.
 //
+// --wire-quant mxfp8 (bf16, more than one rank): the communicator quantizes
+// (comm_quant.cpp), so the expected values are what the host reference of the
+// wire format (dlnb/wire_quant.hpp) makes of the same patterns, stage by stage
+// as the communicator defines each operation, and results are compared bit
+// for bit.
+//
 // Reference equivalent: none (DLNetBench relies on nccl-tests externally).
 #include <chrono>
 #include <cmath>
@@ -35,6 +41,7 @@
 #include <unistd.h>
 
 #include "dlnb/strategy.hpp"
+#include "dlnb/wire_quant.hpp"
 #include "dlnb/xgmi.hpp"
 
 namespace dlnb {
@@ -137,6 +144,82 @@ struct Tester {
   std::vector<Buffer>* pool = nullptr;
   // also check an in-place all-to-all (backends that support it: xgmi)
   bool inplace_a2a = false;
+  // --wire-quant mxfp8: expected values from the host reference (q_* below)
+  bool wire_quant = false;
+  bool quant() const { return wire_quant && t == DType::BF16 && W > 1; }
+  using Half = std::vector<uint16_t>;
+  static Half halves(const std::vector<char>& h) {
+    Half v(h.size() / 2);
+    std::memcpy(v.data(), h.data(), v.size() * 2);
+    return v;
+  }
+  // one message block of n elements through the wire and back
+  static Half q_roundtrip(const Half& x) {
+    std::vector<uint8_t> w(mx_wire_bytes(x.size()));
+    mx_quantize_host(x.data(), x.size(), x.size(), 1, w.data());
+    Half y(x.size());
+    mx_dequantize_host(w.data(), x.size(), 1, y.data(), x.size());
+    return y;
+  }
+  // the rank-ordered quantized sum of one block per rank (qgZ)
+  static Half q_reduce(const std::vector<Half>& per_rank) {
+    const size_t n = per_rank[0].size(), wb = mx_wire_bytes(n);
+    std::vector<uint8_t> w(wb * per_rank.size());
+    for (size_t r = 0; r < per_rank.size(); ++r) mx_quantize_host(per_rank[r].data(), n, n, 1, w.data() + r * wb);
+    Half y(n);
+    mx_dequant_reduce_host(w.data(), n, per_rank.size(), y.data(), n);
+    return y;
+  }
+  Half q_all_gather(size_t off, size_t n) {
+    Half out;
+    for (int r = 0; r < W; ++r) {
+      Half y = q_roundtrip(halves(pattern(r, off, n)));
+      out.insert(out.end(), y.begin(), y.end());
+    }
+    return out;
+  }
+  Half q_reduce_scatter(size_t off, size_t n) {
+    std::vector<Half> blocks;
+    for (int r = 0; r < W; ++r) blocks.push_back(halves(red_pattern(r, off + static_cast<size_t>(me) * n, n)));
+    return q_reduce(blocks);
+  }
+  Half q_all_to_all(size_t off, size_t n) {
+    Half out;
+    for (int p = 0; p < W; ++p) {
+      Half y = q_roundtrip(halves(pattern(p, off + static_cast<size_t>(me) * n, n)));
+      out.insert(out.end(), y.begin(), y.end());
+    }
+    return out;
+  }
+  // W chunks of c = round_up(ceil(n / W), 32) elements (zero tail): chunk d is
+  // reduced as above, rounded to bf16, sent through the wire again
+  Half q_all_reduce(size_t off, size_t n) {
+    const size_t Wz = static_cast<size_t>(W), c = mx_padded((n + Wz - 1) / Wz);
+    std::vector<Half> in;
+    for (int r = 0; r < W; ++r) {
+      in.push_back(halves(red_pattern(r, off, n)));
+      in.back().resize(c * Wz, 0);
+    }
+    Half out;
+    for (size_t d = 0; d < Wz; ++d) {
+      std::vector<Half> blocks;
+      for (int r = 0; r < W; ++r) blocks.emplace_back(in[static_cast<size_t>(r)].begin() + d * c, in[static_cast<size_t>(r)].begin() + (d + 1) * c);
+      Half y = q_roundtrip(q_reduce(blocks));
+      out.insert(out.end(), y.begin(), y.end());
+    }
+    out.resize(n);
+    return out;
+  }
+  void expect_bits(const char* what, size_t n, const std::vector<char>& got, const Half& want) {
+    const Half g = halves(got);
+    for (size_t i = 0; i < want.size(); ++i) {
+      if (i < g.size() && g[i] == want[i]) continue;
+      if (failures < 10)
+        std::fprintf(stderr, "[commtest] rank %d %s n=%zu: element %zu = 0x%04x, expected 0x%04x (quantized wire)\n", me,
+                     what, n, i, i < g.size() ? g[i] : 0u, want[i]);
+      ++failures;
+    }
+  }
   // Buffer i of at least `bytes`: a fresh allocation kept in `keep`, or the
   // registered pool's buffer i.
   void* get(std::vector<Buffer>& keep, size_t bytes, size_t i) {
@@ -196,38 +279,50 @@ struct Tester {
     poison(b, n * es);
     comm.all_reduce(a, b, n, t, s);
     auto got = download(b, n * es);
-    for (size_t i = 0; i < n; ++i) expect("all_reduce", n, got, i, sum_over_ranks(i));
+    if (quant()) expect_bits("all_reduce", n, got, q_all_reduce(0, n));
+    else
+      for (size_t i = 0; i < n; ++i) expect("all_reduce", n, got, i, sum_over_ranks(i));
     // all-reduce in place (fresh input: an out-of-place op must not have touched it, but check that apart)
     upload(a, red_pattern(me, 0, n));
     comm.all_reduce(a, a, n, t, s);
     got = download(a, n * es);
-    for (size_t i = 0; i < n; ++i) expect("all_reduce(in-place)", n, got, i, sum_over_ranks(i));
+    if (quant()) expect_bits("all_reduce(in-place)", n, got, q_all_reduce(0, n));
+    else
+      for (size_t i = 0; i < n; ++i) expect("all_reduce(in-place)", n, got, i, sum_over_ranks(i));
     // all-gather
     upload(a, pattern(me, 0, n));
     poison(b, n * W * es);
     comm.all_gather(a, b, n, t, s);
     got = download(b, n * W * es);
-    for (int r = 0; r < W; ++r)
-      for (size_t i = 0; i < n; ++i) expect("all_gather", n, got, r * n + i, val(r, i));
+    if (quant()) expect_bits("all_gather", n, got, q_all_gather(0, n));
+    else
+      for (int r = 0; r < W; ++r)
+        for (size_t i = 0; i < n; ++i) expect("all_gather", n, got, r * n + i, val(r, i));
     // reduce-scatter: send has W blocks of n, element j = red(me, j)
     upload(a, red_pattern(me, 0, n * W));
     poison(b, n * es);
     comm.reduce_scatter(a, b, n, t, s);
     got = download(b, n * es);
-    for (size_t i = 0; i < n; ++i) expect("reduce_scatter", n, got, i, sum_over_ranks(me * n + i));
+    if (quant()) expect_bits("reduce_scatter", n, got, q_reduce_scatter(0, n));
+    else
+      for (size_t i = 0; i < n; ++i) expect("reduce_scatter", n, got, i, sum_over_ranks(me * n + i));
     // all-to-all: block p of rank r's send = data(r, p*n + i) -> recv block p on me = data(p, me*n + i)
     upload(a, pattern(me, 0, n * W));
     poison(b, n * W * es);
     comm.all_to_all(a, b, n, t, s);
     got = download(b, n * W * es);
-    for (int p = 0; p < W; ++p)
-      for (size_t i = 0; i < n; ++i) expect("all_to_all", n, got, p * n + i, val(p, me * n + i));
+    if (quant()) expect_bits("all_to_all", n, got, q_all_to_all(0, n));
+    else
+      for (int p = 0; p < W; ++p)
+        for (size_t i = 0; i < n; ++i) expect("all_to_all", n, got, p * n + i, val(p, me * n + i));
     if (inplace_a2a) {
       upload(a, pattern(me, 0, n * W));
       comm.all_to_all(a, a, n, t, s);
       got = download(a, n * W * es);
-      for (int p = 0; p < W; ++p)
-        for (size_t i = 0; i < n; ++i) expect("all_to_all(in-place)", n, got, p * n + i, val(p, me * n + i));
+      if (quant()) expect_bits("all_to_all(in-place)", n, got, q_all_to_all(0, n));
+      else
+        for (int p = 0; p < W; ++p)
+          for (size_t i = 0; i < n; ++i) expect("all_to_all(in-place)", n, got, p * n + i, val(p, me * n + i));
     }
     s.synchronize();
     if (failures != before) std::fprintf(stderr, "[commtest] rank %d: n=%zu FAILED\n", me, n);
@@ -270,17 +365,27 @@ struct Tester {
       for (void* out : {ar_out, ag_out, rs_out, a2a_out, p_out}) poison(out, nb);
       g->launch(s);
       auto got = download(ar_out, n * es);
-      for (size_t i = 0; i < n; ++i) expect("graph all_reduce", n, got, i, sum_over_ranks(o + i));
+      if (quant()) expect_bits("graph all_reduce", n, got, q_all_reduce(o, n));
+      else
+        for (size_t i = 0; i < n; ++i) expect("graph all_reduce", n, got, i, sum_over_ranks(o + i));
       got = download(ar_ip, n * es);
-      for (size_t i = 0; i < n; ++i) expect("graph all_reduce(in-place)", n, got, i, sum_over_ranks(o + i));
+      if (quant()) expect_bits("graph all_reduce(in-place)", n, got, q_all_reduce(o, n));
+      else
+        for (size_t i = 0; i < n; ++i) expect("graph all_reduce(in-place)", n, got, i, sum_over_ranks(o + i));
       got = download(ag_out, n * W * es);
-      for (int r = 0; r < W; ++r)
-        for (size_t i = 0; i < n; ++i) expect("graph all_gather", n, got, r * n + i, val(r, o + i));
+      if (quant()) expect_bits("graph all_gather", n, got, q_all_gather(o, n));
+      else
+        for (int r = 0; r < W; ++r)
+          for (size_t i = 0; i < n; ++i) expect("graph all_gather", n, got, r * n + i, val(r, o + i));
       got = download(rs_out, n * es);
-      for (size_t i = 0; i < n; ++i) expect("graph reduce_scatter", n, got, i, sum_over_ranks(o + me * n + i));
+      if (quant()) expect_bits("graph reduce_scatter", n, got, q_reduce_scatter(o, n));
+      else
+        for (size_t i = 0; i < n; ++i) expect("graph reduce_scatter", n, got, i, sum_over_ranks(o + me * n + i));
       got = download(a2a_out, n * W * es);
-      for (int p = 0; p < W; ++p)
-        for (size_t i = 0; i < n; ++i) expect("graph all_to_all", n, got, p * n + i, val(p, o + me * n + i));
+      if (quant()) expect_bits("graph all_to_all", n, got, q_all_to_all(o, n));
+      else
+        for (int p = 0; p < W; ++p)
+          for (size_t i = 0; i < n; ++i) expect("graph all_to_all", n, got, p * n + i, val(p, o + me * n + i));
       if (W > 1) {
         got = download(p_out, n * es);
         for (size_t i = 0; i < n; ++i) expect("graph send/recv", n, got, i, val(prev, o + i));
@@ -316,6 +421,7 @@ std::unique_ptr<CommFactory> factory_for(Context& ctx, const std::string& b) {
   else if (b == "mixed") f = make_mixed_factory(ctx.hg(), *ctx.dev);
   else if (b == "cpu") f = make_shm_factory(ctx.hg(), *ctx.dev);
   else DLNB_THROW("commtest --suite: unknown backend " << b << " (rccl, xgmi, mixed, cpu)");
+  f = wrap_comm_quant(std::move(f), *ctx.dev, ctx.opt.wire_quant, &ctx.wire_quant);
   return wrap_comm_faults(std::move(f), *ctx.dev, ctx.rank());
 }
 
@@ -396,6 +502,7 @@ int run_suite(Context& ctx, const std::vector<std::string>& backends, const std:
             Tester T{ctx, *comm, *stream, t, dtype_size(t), W, me};
             T.pool = pool.empty() ? nullptr : &pool;
             T.inplace_a2a = comm->backend_name() == "XGMI";
+            T.wire_quant = ctx.opt.wire_quant == "mxfp8";
             std::string error;
             try {
               for (size_t n : sizes) {
@@ -506,7 +613,7 @@ int info_main(int argc, char** argv) {
 
 int commtest_main(int argc, char** argv) {
   std::string backend = "auto", devices, dtype = "bf16", sizes_s, json_path, backends_s = "rccl,xgmi",
-              dtypes_s = "bf16,fp8_e4m3";
+              dtypes_s = "bf16,fp8_e4m3", wire_quant = "none";
   bool bench = false, graph = false, registered = false, suite = false, fallback = false;
   int iters = 20, warmup = 5, ranks = 2;
   for (int i = 1; i < argc; ++i) {
@@ -530,12 +637,16 @@ int commtest_main(int argc, char** argv) {
     else if (a == "--warmup") warmup = std::stoi(val("--warmup"));
     else if (a == "--ranks") ranks = std::stoi(val("--ranks"));
     else if (a == "--json") json_path = val("--json");
+    else if (a == "--wire-quant") wire_quant = val("--wire-quant");
     else if (a == "-h" || a == "--help") {
       std::cout << "Usage: dlnb commtest [--backend auto|rccl|xgmi|mixed|cpu|loopback|loopback-cpu] [--ranks N] [-d 0,1,..]\n"
                    "                     [--dtype bf16|fp16|fp32|fp8_e4m3|fp8_e5m2]\n"
                    "                     [--sizes n1,n2,..] [--bench] [--iters N] [--warmup N] [--graph]\n"
+                   "                     [--wire-quant none|mxfp8]\n"
                    "  sizes are elements per rank; check mode verifies every collective exactly\n"
                    "  --graph: capture the operations into a HIP graph and replay it (rccl, xgmi)\n"
+                   "  --wire-quant mxfp8: bf16 collectives travel as MXFP8 wire blocks; the check compares bit for bit\n"
+                   "       with the host reference of the wire format\n"
                    "  --registered: peer-memory buffers registered with the communicator (zero-copy paths)\n"
                    "       dlnb commtest --suite [--backends rccl,xgmi] [--dtypes bf16,fp8_e4m3] [--sizes ..]\n"
                    "                     [--release-fallback] [--json PATH]\n"
@@ -547,6 +658,7 @@ int commtest_main(int argc, char** argv) {
   auto body = [&](std::unique_ptr<Bootstrap> boot) -> int {
   Context ctx;
   ctx.boot = std::move(boot);
+  ctx.opt.wire_quant = wire_quant;
   if (suite) {
     std::vector<std::string> bs, ds;
     for (auto& x : split(backends_s, ',')) bs.push_back(trim(x));
@@ -564,6 +676,9 @@ int commtest_main(int argc, char** argv) {
   const std::string be = select_backend(ctx, backend, devices);
   DLNB_REQUIRE(!graph || be == "rccl" || be == "xgmi" || be == "mixed", "commtest --graph needs a GPU backend");
   const DType t = parse_dtype(dtype);
+  DLNB_REQUIRE(wire_quant == "none" || t == DType::BF16,
+               "commtest: --wire-quant " << wire_quant << " quantizes bf16 collectives: it cannot be combined with --dtype "
+                                         << dtype);
   const int W = ctx.world(), me = ctx.rank();
   std::vector<size_t> sizes;
   if (sizes_s.empty()) {
@@ -584,6 +699,7 @@ int commtest_main(int argc, char** argv) {
   auto stream = ctx.dev->create_stream(true);
   Tester T{ctx, *comm, *stream, t, es, W, me};
   T.inplace_a2a = comm->backend_name() == "XGMI";
+  T.wire_quant = wire_quant == "mxfp8";
   const bool reg = registered && comm->wants_peer_buffers();
   std::vector<Buffer> pool;
   if (reg && !bench) {
@@ -626,6 +742,7 @@ int commtest_main(int argc, char** argv) {
       j["registered"] = reg;
       j["world_size"] = W;
       j["dtype"] = dtype_name(t);
+      if (wire_quant != "none") j["wire_quant"] = wire_quant;
       Json sz = Json::array();
       for (size_t n : sizes) sz.push_back(static_cast<double>(n));
       j["sizes"] = sz;

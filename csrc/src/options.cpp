@@ -79,6 +79,8 @@ std::string usage(StrategyKind kind, const std::string& prog) {
      << "                         (loopback-cpu: on the CPU device), default 2\n"
      << "  --compute C            auto | sleep | spin | gemm | gemm-work | flops\n"
      << "  --wire-dtype T         bf16 | fp16 | fp32 | fp8 (collective element type)\n"
+     << "  --wire-quant Q         none | mxfp8: bf16 collectives are quantized block-wise (MXFP8 E4M3, 32 elements\n"
+     << "                         per e8m0 scale) before the transport and dequantized after it (--wire-dtype bf16)\n"
      << "  --compute-dtype T      auto | bf16 | fp8 (GEMM operand type for gemm/flops)\n"
      << "  --schedule S           overlap (stream-ordered) | reference (blocking like DLNetBench)\n"
      << "  --tp-granularity G     microbatch | layer (hybrid_3d, hybrid_4d)\n"
@@ -158,6 +160,8 @@ Options parse_options(StrategyKind kind, int argc, const char* const* argv) {
       o.compute = val("compute");
     } else if (is("--wire-dtype") || is("--dtype")) {
       o.wire_dtype = val("wire-dtype");
+    } else if (is("--wire-quant")) {
+      o.wire_quant = val("wire-quant");
     } else if (is("--compute-dtype")) {
       o.compute_dtype = val("compute-dtype");
     } else if (is("--schedule")) {
@@ -286,6 +290,10 @@ Options parse_options(StrategyKind kind, int argc, const char* const* argv) {
   DLNB_REQUIRE(o.zero >= 0 && o.zero <= 2, "--zero must be 0, 1 or 2 (ZeRO-3 is the fsdp strategy)");
   DLNB_REQUIRE(o.zero == 0 || kind == StrategyKind::DP, "--zero applies to dp");
   DLNB_REQUIRE(o.time_scale > 0, "--time-scale must be > 0");
+  DLNB_REQUIRE(o.wire_quant == "none" || o.wire_quant == "mxfp8", "--wire-quant must be none or mxfp8");
+  DLNB_REQUIRE(o.wire_quant == "none" || parse_dtype(o.wire_dtype) == DType::BF16,
+               "--wire-quant " << o.wire_quant << " quantizes bf16 collectives: it cannot be combined with --wire-dtype "
+                               << o.wire_dtype);
   return o;
 }
 

@@ -67,6 +67,24 @@ void rank_maxima(const std::vector<Json>& ranks, Json& ext) {
   ext["chain_capped"] = c;
 }
 
+// `wire_quant`: what rank 0's communicators quantized (comm.hpp WireQuantCounts).
+Json wire_quant_json(const WireQuantCounts& c) {
+  static const char* const names[4] = {"all_reduce", "all_gather", "reduce_scatter", "all_to_all"};
+  Json ops = Json::object();
+  for (int k = 0; k < 4; ++k) {
+    Json o = Json::object();
+    o["calls"] = static_cast<long long>(c.ops[k].calls);
+    o["payload_bytes"] = static_cast<long long>(c.ops[k].payload_bytes);
+    o["wire_bytes"] = static_cast<long long>(c.ops[k].wire_bytes);
+    ops[names[k]] = o;
+  }
+  Json j = Json::object();
+  j["format"] = "mxfp8_e4m3";
+  j["block"] = 32;
+  j["ops"] = ops;
+  return j;
+}
+
 }  // namespace
 
 Json rank_report(Context& ctx, Strategy& strat, const TimedRuns& tr, const Replay& replay) {
@@ -160,6 +178,7 @@ Json global_report(Context& ctx, Strategy& strat, const RunSetup& setup, const T
   // before, released by a host store; DLNB_PREARM=0 launches in the loop)
   ext["prearm"] = replay.prearmed();
   ext["wire_dtype"] = dtype_name(ctx.wire);
+  if (opt.wire_quant != "none") ext["wire_quant"] = wire_quant_json(ctx.wire_quant);
   ext["compute"] = ctx.compute->describe();
   ext["stats_file"] = setup.stats_path;
   ext["stats_dtype"] = ctx.stats.dtype;

@@ -393,6 +393,7 @@ std::string select_backend(Context& ctx, const std::string& requested, const std
   } else {
     DLNB_THROW("unknown backend '" << backend << "' (auto, rccl, xgmi, mixed, cpu, loopback, loopback-cpu)");
   }
+  ctx.comms = wrap_comm_quant(std::move(ctx.comms), *ctx.dev, ctx.opt.wire_quant, &ctx.wire_quant);
   ctx.comms = wrap_comm_faults(std::move(ctx.comms), *ctx.dev, ri.rank);
   ctx.comms.reset(new RecordingFactory(std::move(ctx.comms), &ctx.comm_log, &ctx.live_comms));
   return backend;

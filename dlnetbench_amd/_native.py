@@ -89,6 +89,14 @@ def lib() -> ctypes.CDLL:
     L.dlnb_hbm_stream.argtypes = [c_vp, c_vp, c_vp, c_size, c_dbl, c_int, c_int, c_vp, c_vp, c_vp, c_vp]
     L.dlnb_hbm_chunk_bytes.restype = c_size
     L.dlnb_stamp.argtypes = [c_vp, c_vp]
+    L.dlnb_mx_wire_bytes.argtypes = [c_size]
+    L.dlnb_mx_wire_bytes.restype = c_size
+    L.dlnb_mx_quantize.argtypes = [c_vp, c_size, c_size, c_size, c_vp, c_vp]
+    L.dlnb_mx_dequantize.argtypes = [c_vp, c_size, c_size, c_vp, c_size, c_vp]
+    L.dlnb_mx_dequant_reduce.argtypes = [c_vp, c_size, c_size, c_vp, c_size, c_vp]
+    L.dlnb_mx_quantize_host.argtypes = [c_vp, c_size, c_size, c_size, c_vp]
+    L.dlnb_mx_dequantize_host.argtypes = [c_vp, c_size, c_size, c_vp, c_size]
+    L.dlnb_mx_dequant_reduce_host.argtypes = [c_vp, c_size, c_size, c_vp, c_size]
     L.dlnb_wallclock_hz.argtypes = [c_int]
     L.dlnb_wallclock_hz.restype = c_dbl
     L.dlnb_bf16_to_float.argtypes = [ctypes.c_ushort]

@@ -31,6 +31,7 @@ POSITIONAL = {
 _FLAG = {
     "warmup": "-w", "runs": "-r", "devices": "-d", "min_exectime": "-m",
     "backend": "--backend", "compute": "--compute", "wire_dtype": "--wire-dtype",
+    "wire_quant": "--wire-quant",
     "compute_dtype": "--compute-dtype", "schedule": "--schedule", "tp_granularity": "--tp-granularity",
     "dp_buckets": "--dp-buckets", "dp_bucket_ratio": "--dp-bucket-ratio", "max_loop_iters": "--max-loop-iters", "time_scale": "--time-scale",
     "json": "--json", "store": "--store", "stats_file": "--stats-file", "comm_cus": "--comm-cus",
