@@ -9,7 +9,8 @@
 //           reference parity.
 //   spin  - every CU runs dependent VALU work until the deadline.
 //   gemm  - (default on GPU) hand-written MFMA GEMM shaped from the model
-//           (M = 8192-token chunk, N = FFN dim, K = hidden dim) run as a
+//           (the FFN down projection: M = 8192-token chunk, N = hidden dim,
+//           K = FFN dim) run as a
 //           persistent kernel on every CU that stops at a device-clock
 //           deadline: exactly the table's duration, with the matrix cores
 //           and HBM as busy as in training (the reference's usleep leaves

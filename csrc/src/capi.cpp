@@ -5,11 +5,13 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <sstream>
 #include <string>
 #include <vector>
 
 #include "dlnb/compute.hpp"
 #include "dlnb/kernels.hpp"
+#include "dlnb/program.hpp"
 #include "dlnb/strategy.hpp"
 #include "dlnb/wire_quant.hpp"
 #include "dlnb/workload.hpp"
@@ -198,6 +200,95 @@ int dlnb_gemm_program(const void* A, const void* B, void* C, int M, int N, int K
     dlnb::kernels::gemm_tn_deadline_program(A, B, C, M, N, K, static_cast<dlnb::DType>(dtype),
                                             static_cast<const dlnb::kernels::DlTask*>(task_buf), n,
                                             static_cast<uint64_t*>(slot), grid, stream, epoch);
+  });
+}
+
+// The compute program builder (dlnb/program.hpp) driven by a text script, one
+// op per line, for the tests (no device):
+//   begin | wait G TAG | record G TAG | task TICKS ROUNDS TAIL [G TAG [G TAG]]
+//   | join DONE TAG [G ...] | timeout TICKS | flush | end JOIN_OK
+// Gates and the done word are small integers (0: none) that stand for fake
+// addresses and are printed back as those integers. *out: {"launches": the
+// task list every flush / end took, "joined": whether the last end took the join}.
+int dlnb_program_script(const char* script, int fixed_work, char** out) {
+  using dlnb::Json;
+  using dlnb::kernels::DlTask;
+  return guard([&] {
+    auto ptr = [](unsigned long long n) { return reinterpret_cast<uint64_t*>(n * 16); };
+    auto num = [](const void* p) { return static_cast<long long>(reinterpret_cast<uintptr_t>(p) / 16); };
+    dlnb::kernels::DlSync base;
+    base.iter = ptr(1001);
+    base.counters = ptr(1002);
+    base.gate_timeout = 60;
+    base.abort = ptr(1004);
+    dlnb::ProgramBuilder b([&base] { return base; }, fixed_work != 0);
+    dlnb::ProgramJoin join;
+    bool have_join = false, joined = false;
+    Json launches = Json::array();
+    auto launch = [&] {
+      Json list = Json::array();
+      for (const DlTask& t : b.take()) {
+        Json j = Json::object();
+        j["ticks"] = t.ticks;
+        j["epoch"] = t.epoch;
+        j["rounds"] = t.work_rounds;
+        j["tail"] = t.tail_kt;
+        j["flags"] = t.flags;
+        j["gates"] = std::vector<long long>{num(t.sync.gate[0]), t.sync.tag[0], num(t.sync.gate[1]), t.sync.tag[1]};
+        j["done"] = std::vector<long long>{num(t.sync.done_gate), t.sync.done_tag};
+        j["tstart"] = std::vector<long long>{num(t.sync.tstart[0]), num(t.sync.tstart[1])};
+        j["gate_timeout"] = t.sync.gate_timeout;
+        j["base"] = t.sync.iter == base.iter && t.sync.counters == base.counters && t.sync.abort == base.abort;
+        list.push_back(j);
+      }
+      launches.push_back(list);
+    };
+    std::istringstream lines(script);
+    for (std::string line; std::getline(lines, line);) {
+      std::istringstream in(line);
+      std::string op;
+      if (!(in >> op)) continue;
+      std::vector<unsigned long long> a;
+      for (unsigned long long v; in >> v;) a.push_back(v);
+      const size_t n = a.size();
+      a.resize(std::max<size_t>(n, 7), 0);
+      if (op == "begin") {
+        b.begin();
+      } else if (op == "wait") {
+        b.fold_wait(ptr(a[0]), static_cast<uint32_t>(a[1]));
+      } else if (op == "record") {
+        b.fold_record(ptr(a[0]), static_cast<uint32_t>(a[1]));
+      } else if (op == "task") {
+        DlTask t;
+        t.sync = base;
+        t.ticks = a[0];
+        t.work_rounds = static_cast<uint32_t>(a[1]);
+        t.tail_kt = static_cast<uint32_t>(a[2]);
+        for (int i = 0; i < 2; ++i) {
+          t.sync.gate[i] = ptr(a[3 + 2 * i]);
+          t.sync.tag[i] = static_cast<uint32_t>(a[4 + 2 * i]);
+        }
+        b.append(t);
+      } else if (op == "join") {
+        join = dlnb::ProgramJoin{{}, static_cast<uint32_t>(a[1]), ptr(a[0])};
+        for (size_t i = 2; i < n; ++i) join.gates.push_back(ptr(a[i]));
+        have_join = true;
+      } else if (op == "timeout") {
+        base.gate_timeout = a[0];
+      } else if (op == "flush") {
+        launch();
+      } else if (op == "end") {
+        joined = b.end(have_join && a[0] ? &join : nullptr);
+        if (joined) have_join = false;
+        launch();
+      } else {
+        DLNB_THROW("dlnb_program_script: unknown op '" << op << "'");
+      }
+    }
+    Json doc = Json::object();
+    doc["launches"] = launches;
+    doc["joined"] = joined;
+    if (out) *out = dup(doc.dump());
   });
 }
 

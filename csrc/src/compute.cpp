@@ -7,6 +7,7 @@
 #include <set>
 
 #include "dlnb/kernels.hpp"
+#include "dlnb/program.hpp"
 #include "dlnb/timers.hpp"
 
 namespace dlnb {
@@ -86,6 +87,55 @@ struct FixedWork {
   double us = 0.0;
 };
 
+// The hbm mode's arrays, launches and report block.
+struct HbmStream {
+  Buffer a, b, c;
+  Buffer totals;     // {chunks, ticks} the kernels add to (kernels::hbm_stream)
+  size_t bytes = 0;  // per array (a whole number of chunks)
+
+  // Three bf16 arrays of 512 MiB: each alone is twice the 256 MiB Infinity
+  // Cache, so the sweep cannot live in cache. Halved while the set exceeds
+  // `share` bytes (the GEMM operands' rule); always a whole number of chunks.
+  void setup(Device& dev, double share) {
+    bytes = size_t(512) << 20;
+    while (bytes > kernels::kHbmChunkBytes && share > 0 && 3.0 * static_cast<double>(bytes) > share) bytes /= 2;
+    a = dev.alloc(bytes);
+    b = dev.alloc(bytes);
+    c = dev.alloc(bytes);
+    totals = dev.alloc(2 * sizeof(uint64_t));
+    auto s = dev.create_stream(false);
+    dev.fill_random(a.data(), bytes / 2, DType::BF16, 1, *s);
+    dev.fill_random(b.data(), bytes / 2, DType::BF16, 2, *s);
+    dev.memset_async(totals.data(), 0, 2 * sizeof(uint64_t), *s);
+    // the kernel's first launch (code object load, the one-block-per-CU
+    // check) here, never inside a graph capture: one chunk, counted nowhere
+    kernels::hbm_stream(a.data(), b.data(), c.data(), kernels::kHbmChunkBytes / 2, 0, 1, s->native());
+    s->synchronize();
+  }
+  void task(Stream& s, uint64_t ticks, int grid, uint64_t* start, uint64_t* extra) {
+    kernels::hbm_stream(a.data(), b.data(), c.data(), bytes / 2, std::max<uint64_t>(ticks, 1), grid, s.native(), start,
+                        extra, totals.as<uint64_t>(), nullptr);
+  }
+  // What the streaming tasks moved so far (device totals: every launch and
+  // every replay of a captured one adds to them) in the time they ran.
+  Json report(Device& dev, int grid, double hz) const {
+    uint64_t v[2] = {0, 0};
+    auto st = dev.create_stream(false);
+    dev.copy_async(v, totals.data(), sizeof(v), *st);
+    st->synchronize();
+    Json h = Json::object();
+    h["working_set_bytes"] = static_cast<double>(3 * bytes);
+    h["chunk_bytes"] = static_cast<double>(kernels::kHbmChunkBytes);
+    h["grid"] = grid;
+    const double moved = 3.0 * static_cast<double>(kernels::kHbmChunkBytes) * static_cast<double>(v[0]);
+    const double busy = static_cast<double>(v[1]) / hz;
+    h["bytes_moved"] = moved;
+    h["busy_s"] = busy;
+    h["GBps"] = busy > 0 ? moved / busy / 1e9 : 0.0;
+    return h;
+  }
+};
+
 class GpuCompute : public ComputeEngine {
  public:
   GpuCompute(Device& dev, ComputeMode mode, const ComputeShape& shape, double scale)
@@ -99,104 +149,19 @@ class GpuCompute : public ComputeEngine {
                                                 kernels::wallclock_hz_nominal(dev.index()));
     dtype_ = shape.dtype == DType::FP8_E4M3 ? DType::FP8_E4M3 : DType::BF16;
     fixed_ = mode_ == ComputeMode::GemmWork || mode_ == ComputeMode::Flops;
-    // The stand-in is the layer's FFN down projection, C[tokens, hidden] =
-    // A[tokens, ffn] . W[hidden, ffn]^T: its long K (the FFN width) keeps
-    // the per-tile pipeline fill / drain of the persistent kernel small. At
-    // the up-projection shape used before (K = hidden) the deadline kernel did
-    // 0.725 -> 0.787 less MFMA busy per clock on its CUs (bf16 llama3_8b) and
-    // 1810 vs 2672 TF/s (fp8 ViT-H, K = 1280) (profiles/deadline_shapes_r3.md).
-    // K: a multiple of 128 (bf16: an even K-tile count, the balanced body) or
-    // 256 bytes (fp8: the one-wave-per-SIMD MX kernel).
-    const int kmul = dtype_ == DType::FP8_E4M3 ? 256 : 128;
-    K_ = std::min(65536, std::max(512, (shape.ffn + kmul - 1) / kmul * kmul));
-    N_ = std::min(32768, std::max(1024, (shape.hidden + 255) / 256 * 256));
-    // The operands must fit beside the strategy's buffers: at most 1/8 of this
-    // rank's share of free memory (ranks sharing the GPU each allocate their
-    // own set). Large-FFN models (K = ffn up to 64 Ki) shrink K, keeping its
-    // multiple (ffn 53248 x hidden 16384 is ~2.6 GB per rank).
-    if (gemm_mode()) {
-      const size_t esz = dtype_size(dtype_);
-      const double share = static_cast<double>(dev_.free_memory()) / std::max(1, shape.ranks_on_device) / 8.0;
-      auto bytes = [&](int k) {
-        return static_cast<double>(kMmax + N_) * k * esz + static_cast<double>(kMmax) * N_ * 2;
-      };
-      while (K_ > 512 && share > 0 && bytes(K_) > share) K_ = std::max(512, (K_ / 2 + kmul - 1) / kmul * kmul);
-    }
-    // GEMM operands for every GEMM mode
+    choose_shape(shape);
     if (gemm_mode()) alloc_operands();
     if (mode_ == ComputeMode::Hbm) {
-      // Three bf16 arrays of 512 MiB: each alone is twice the 256 MiB Infinity
-      // Cache, so the sweep cannot live in cache. Halved while the set exceeds
-      // 1/8 of this rank's share of free memory (the GEMM operands' rule);
-      // always a whole number of chunks. The grid leaves comm_cus CUs free
-      // (one block per CU, hbm_stream.hip), as the GEMM's does.
-      hbm_bytes_ = size_t(512) << 20;
-      const double share = static_cast<double>(dev_.free_memory()) / std::max(1, shape.ranks_on_device) / 8.0;
-      while (hbm_bytes_ > kernels::kHbmChunkBytes && share > 0 && 3.0 * static_cast<double>(hbm_bytes_) > share)
-        hbm_bytes_ /= 2;
-      grid_ = std::max(1, cus_ - std::max(0, shape.comm_cus));
-      // Ranks sharing the device split those CUs: a block that found no CU
-      // until another rank's task ended would run its whole deadline from
-      // there, and the task would last up to twice the table's time.
-      grid_ = std::max(1, grid_ / std::max(1, shape.ranks_on_device));
-      A_ = dev_.alloc(hbm_bytes_);
-      B_ = dev_.alloc(hbm_bytes_);
-      C_ = dev_.alloc(hbm_bytes_);
-      hbm_totals_ = dev_.alloc(2 * sizeof(uint64_t));
-      auto s = dev_.create_stream(false);
-      dev_.fill_random(A_.data(), hbm_bytes_ / 2, DType::BF16, 1, *s);
-      dev_.fill_random(B_.data(), hbm_bytes_ / 2, DType::BF16, 2, *s);
-      dev_.memset_async(hbm_totals_.data(), 0, 2 * sizeof(uint64_t), *s);
-      // the kernel's first launch (code object load, the one-block-per-CU
-      // check) here, never inside a graph capture: one chunk, counted nowhere
-      kernels::hbm_stream(A_.data(), B_.data(), C_.data(), kernels::kHbmChunkBytes / 2, 0, 1, s->native());
-      s->synchronize();
+      // The grid leaves comm_cus CUs free (one block per CU, hbm_stream.hip),
+      // as the GEMM's does. Ranks sharing the device split those CUs: a block
+      // that found no CU until another rank's task ended would run its whole
+      // deadline from there, and the task would last up to twice the table's time.
+      grid_ = free_cus(shape, true);
+      hbm_.setup(dev_, memory_share(shape));
     }
-    if (mode_ == ComputeMode::Gemm || fixed_) {
-      // one 64-byte line per compute stream; the counters (DlCounter)
-      slots_ = dev_.alloc(kSlots * 64);
-      counters_ = dev_.alloc(kernels::kNumCounters * sizeof(uint64_t));
-      // compute programs' task lists: a device ring (lists captured into a
-      // graph, uploaded after the capture) and a host-mapped ring (lists
-      // launched at once: written by the host, read by the kernel, no copy)
-      prog_dev_ = dev_.alloc(kProgTasks * sizeof(kernels::DlTask));
-      prog_host_ = reinterpret_cast<kernels::DlTask*>(dev_.alloc_stamps(kProgTasks * sizeof(kernels::DlTask) / 8));
-      auto zs = dev_.create_stream(false);
-      dev_.memset_async(slots_.data(), 0, kSlots * 64, *zs);
-      dev_.memset_async(counters_.data(), 0, kernels::kNumCounters * sizeof(uint64_t), *zs);
-      zs->synchronize();
-      // Leave `comm_cus` CUs to collectives: one 128-KiB-LDS block fits per
-      // CU, so a grid of CUs - comm_cus blocks never touches those CUs and
-      // RCCL / copy kernels on the high-priority comm streams always find
-      // room (with the whole chip taken, a comm kernel only starts at a
-      // compute boundary, and overlap collapses).
-      grid_ = std::max(1, cus_ - std::max(0, shape.comm_cus));
-      // Fixed work waits for every block of its grid between two tasks, so
-      // ranks sharing the device split the free CUs: all their grids must be
-      // resident at once.
-      if (fixed_) grid_ = std::max(1, grid_ / std::max(1, shape.ranks_on_device));
-    }
-    if (mode_ == ComputeMode::Gemm) {
-      // One launch per task by default. Cutting a task into relaunched
-      // slices (DLNB_GEMM_SLICE_US > 0) was meant to give collectives CUs at
-      // slice boundaries, which the comm_cus reservation already does; at
-      // 500-us slices every slice also abandons a partial 256 x 256 tile and
-      // pays a prologue: 630 vs 679 TF/s per GHz on the headline
-      // (profiles/slice_ab_r3.md), and a 4x larger graph.
-      // Ranks sharing one GPU (loopback, -d 0,0) keep 500-us slices: with one
-      // launch per task a rank's persistent grid holds the CUs for its whole
-      // task and the other ranks' compute (and so the collectives that wait
-      // for it) serialises behind it - 8 loopback ranks of the llama3_8b FSDP
-      // config ran 459 vs 317 ms per iteration (profiles/loopback_w8_r3.md).
-      slice_us_ = static_cast<double>(env_int("DLNB_GEMM_SLICE_US", shape.ranks_on_device > 1 ? 500 : 0));
-    } else {
-      slice_us_ = 0.0;
-    }
-    if (fixed_) {
-      DLNB_REQUIRE(kernels::deadline_program_ok(kMmax, N_, K_, dtype_),
-                   "fixed-work compute: no program kernel for the stand-in shape " << kMmax << "x" << N_ << "x" << K_);
-      calibrate();
-    }
+    if (gemm_mode()) setup_deadline_state(shape);
+    slice_us_ = mode_ == ComputeMode::Gemm ? choose_slice_us(shape) : 0.0;
+    if (fixed_) calibrate();
   }
   ~GpuCompute() override {
     // (a task list a kernel may still read is never freed: the process is going away)
@@ -223,65 +188,35 @@ class GpuCompute : public ComputeEngine {
     if ((mode_ != ComputeMode::Gemm && !fixed_) || slice_us_ > 0 || env_int("DLNB_COMPUTE_PROGRAMS", 1) == 0 ||
         !kernels::deadline_program_ok(kMmax, N_, K_, dtype_))
       return false;
-    Program& p = programs_[&s];
-    DLNB_REQUIRE(!p.open, "begin_program: a program is already open on this stream");
-    p.open = true;
-    p.index = 0;
-    p.tasks.clear();
-    p.pending.clear();
-    p.done_free = false;
-    p.split = false;
-    if (dev_.gate_events()) {
-      // the stream's gate-event waits and records between the tasks become
-      // the tasks' gates and done gates (gate-only tasks where none fits):
-      // no gate kernel on the stream while its program is being built
-      p.fold.e = this;
-      p.fold.s = &s;
-      dev_.set_stream_fold(s, &p.fold);
-    }
+    Lane& l = programs_.try_emplace(&s, *this, s).first->second;
+    l.prog.begin();
+    // the stream's gate-event waits and records between the tasks become
+    // the tasks' gates and done gates (gate-only tasks where none fits):
+    // no gate kernel on the stream while its program is being built
+    if (dev_.gate_events()) dev_.set_stream_fold(s, &l);
     return true;
   }
   void end_program(Stream& s, bool join_ok) override {
     auto it = programs_.find(&s);
-    if (it == programs_.end() || !it->second.open) return;
-    Program& p = it->second;
+    if (it == programs_.end() || !it->second.prog.open()) return;
     dev_.set_stream_fold(s, nullptr);
-    emit_pending(s, p, nullptr, 0);  // waits after the last task: before the join
     auto j = joins_.find(&s);
-    if (j != joins_.end() && !p.tasks.empty() && join_ok) {
-      // the join task(s): up to two gates each, the last one stores the done word
-      const Join& jn = j->second;
-      size_t g = 0;
-      do {
-        kernels::DlTask t;
-        t.sync.iter = dev_.iter_word();
-        t.sync.counters = counters_.as<uint64_t>();
-        t.sync.gate_timeout = gate_timeout_ticks_;
-        t.sync.abort = dev_.abort_word();
-        for (int i = 0; i < 2 && g < jn.gates.size(); ++i, ++g) {
-          t.sync.gate[i] = jn.gates[g];
-          t.sync.tag[i] = jn.tag;
-        }
-        if (g >= jn.gates.size()) t.sync.tstart[0] = jn.host_done;
-        t.ticks = 0;
-        p.tasks.push_back(t);
-      } while (g < jn.gates.size());
+    if (it->second.prog.end(j != joins_.end() && join_ok ? &j->second : nullptr)) {
       joins_.erase(j);
       joined_.insert(&s);
     }
     flush_program(s);
-    p.open = false;
   }
   void set_lane_join(Stream& s, const std::vector<uint64_t*>& gates, uint32_t tag, uint64_t* host_done) override {
     if (mode_ != ComputeMode::Gemm && !fixed_) return;
-    joins_[&s] = Join{gates, tag, host_done};
+    joins_[&s] = ProgramJoin{gates, tag, host_done};
     joined_.erase(&s);
     lane_stats_.clear();
   }
   bool program_joined(Stream& s) override { return joined_.count(&s) != 0; }
   bool program_split(Stream& s) override {
     auto it = programs_.find(&s);
-    return it != programs_.end() && it->second.split;
+    return it != programs_.end() && it->second.prog.split();
   }
   long programs_on(Stream& s) override {
     auto it = program_count_.find(&s);
@@ -338,15 +273,7 @@ class GpuCompute : public ComputeEngine {
       return;
     }
     if (mode_ == ComputeMode::Gemm && us * scale_ >= 20.0 && chain_live_[slot_for(s)]) {
-      note_task(s, us * scale_);
-      if (stall_timers_ && !start) start = stall_timers_->task_slot(s);
-      StartNote note{stall_timers_, s, start, ticks(us * scale_), nullptr};
-      kernels::DlSync sync;
-      sync.tstart[0] = start;
-      sync.tstart[1] = extra_start_;
-      extra_start_ = nullptr;
-      deadline_task(s, us * scale_, sync, true, done);
-      ++chained_;
+      noted_deadline_task(s, us * scale_, {}, start, true, done);
       return;
     }
     run_stamped(s, us, flops, start);
@@ -389,15 +316,7 @@ class GpuCompute : public ComputeEngine {
       ++gated_;
       return;
     }
-    note_task(s, us * scale_);
-    if (stall_timers_ && !start) start = stall_timers_->task_slot(s);
-    StartNote note{stall_timers_, s, start, ticks(us * scale_), nullptr};
-    sync.tstart[0] = start;
-    sync.tstart[1] = extra_start_;
-    extra_start_ = nullptr;
-    const bool chained = chain && chain_live_[slot_for(s)];
-    deadline_task(s, us * scale_, sync, chained, done);
-    if (chained) ++chained_;
+    noted_deadline_task(s, us * scale_, sync, start, chain && chain_live_[slot_for(s)], done);
     ++gated_;
   }
 
@@ -407,28 +326,20 @@ class GpuCompute : public ComputeEngine {
   void flush_program(Stream& s) {
     auto it = programs_.find(&s);
     if (it == programs_.end()) return;
-    // folded waits not taken by a task yet: the launch ends with them (a
-    // kernel of its own follows it on the stream)
-    if (it->second.open) emit_pending(s, it->second, nullptr, 0);
-    if (it->second.tasks.empty()) return;
-    it->second.done_free = false;
-    std::vector<kernels::DlTask>& ts = it->second.tasks;
+    const std::vector<kernels::DlTask> ts = it->second.prog.take();
+    if (ts.empty()) return;
     // A program whose first task waits for gates (FSDP: the iteration's first
     // all-gather) is launched only once they are up, behind one-wave gate
     // waits: resident and waiting, its grid would hold the CUs that
     // collective needs (round 5: the headline's first all-gather ran on the 32
     // free CUs, 0.74 instead of 0.19 ms). Its first block then finds them up.
-    for (int i = 0; i < 2; ++i)
-      if (ts[0].sync.gate[i])
-        kernels::gate_wait(ts[0].sync.gate[i], dev_.iter_word(), ts[0].sync.tag[i], gate_timeout_ticks_,
-                           counters_.as<uint64_t>() + kernels::kWaitTimeouts, s.native(), dev_.abort_word());
+    wait_gates(s, ts[0].sync);
     const kernels::DlTask* dst = place_tasks(s, ts);
     kernels::gemm_tn_deadline_program(A_.data(), B_.data(), C_.data(), kMmax, N_, K_, dtype_, dst,
                                       static_cast<int>(ts.size()), slot_for(s), grid_, s.native(), 0u);
     ++programs_launched_;
     ++program_count_[&s];
     program_tasks_ += static_cast<long>(ts.size());
-    ts.clear();
   }
 
   void run_stamped(Stream& s, double us, double flops, uint64_t* start) override {
@@ -436,53 +347,38 @@ class GpuCompute : public ComputeEngine {
       fixed_task(s, us, flops, start, {}, nullptr);
       return;
     }
-    note_task(s, us * scale_);
-    if (stall_timers_ && !start) start = stall_timers_->task_slot(s);
-    StartNote note{stall_timers_, s, start, ticks(std::max(0.0, us * scale_)), nullptr};
-    double d = us * scale_;
-    // a task that is not a deadline kernel cannot join the open program
-    if (mode_ == ComputeMode::Gemm && d < 20.0) {
-      auto pit = programs_.find(&s);
-      if (pit != programs_.end() && pit->second.open) pit->second.split = true;
-      flush_program(s);
-    }
-    if (mode_ == ComputeMode::Gemm) chain_live_[slot_for(s)] = false;  // a chain restarts at every unchained task
-    if (mode_ == ComputeMode::Sleep || mode_ == ComputeMode::Spin || mode_ == ComputeMode::Hbm) {
-      // the kernel stamps its own start (stall timers: gap() from it)
-      uint64_t* extra = extra_start_;
-      extra_start_ = nullptr;
-      if (d <= 0) {
-        if (start) dev_.stamp(s, start);
-        if (extra) dev_.stamp(s, extra);
-      } else if (mode_ == ComputeMode::Sleep) {
-        kernels::idle_wait(ticks(d), s.native(), start, extra);
-      } else if (mode_ == ComputeMode::Spin) {
-        kernels::busy_spin(ticks(d), cus_, s.native(), start, extra);
-      } else {
-        kernels::hbm_stream(A_.data(), B_.data(), C_.data(), hbm_bytes_ / 2, std::max<uint64_t>(ticks(d), 1), grid_,
-                            s.native(), start, extra, hbm_totals_.as<uint64_t>(), nullptr);
-      }
-      return;
-    }
-    // Fixed duration, real MFMA work: persistent deadline GEMM (the stand-in
-    // keeps the matrix cores and HBM busy for exactly the table's time, so
-    // DVFS or contention changes how much work is done, not how long).
-    if (d <= 0) {
-      if (start) dev_.stamp(s, start);
-      if (extra_start_) dev_.stamp(s, extra_start_);
-      extra_start_ = nullptr;
-      return;
-    }
-    if (d < 20.0) {
-      kernels::busy_spin(ticks(d), cus_, s.native(), start, extra_start_);
-      extra_start_ = nullptr;
-      return;
-    }
+    const double d = us * scale_;
+    note_task(s, d);
+    // every kernel below stamps its own start (stall timers: gap() from it)
     kernels::DlSync sync;
-    sync.tstart[0] = start;
-    sync.tstart[1] = extra_start_;
-    extra_start_ = nullptr;
-    deadline_task(s, d, sync, false);
+    take_start_slots(s, sync, start);
+    uint64_t* const t0 = sync.tstart[0];
+    uint64_t* const t1 = sync.tstart[1];
+    StartNote note{stall_timers_, s, t0, ticks(std::max(0.0, d)), nullptr};
+    if (mode_ == ComputeMode::Gemm) {
+      // a task that is not a deadline kernel cannot join the open program
+      if (d < 20.0) {
+        auto pit = programs_.find(&s);
+        if (pit != programs_.end() && pit->second.prog.open()) pit->second.prog.mark_split();
+        flush_program(s);
+      }
+      chain_live_[slot_for(s)] = false;  // a chain restarts at every unchained task
+    }
+    if (d <= 0) {
+      if (t0) dev_.stamp(s, t0);
+      if (t1) dev_.stamp(s, t1);
+    } else if (mode_ == ComputeMode::Sleep) {
+      kernels::idle_wait(ticks(d), s.native(), t0, t1);
+    } else if (mode_ == ComputeMode::Spin || (mode_ == ComputeMode::Gemm && d < 20.0)) {
+      kernels::busy_spin(ticks(d), cus_, s.native(), t0, t1);
+    } else if (mode_ == ComputeMode::Hbm) {
+      hbm_.task(s, ticks(d), grid_, t0, t1);
+    } else {
+      // Fixed duration, real MFMA work: persistent deadline GEMM (the stand-in
+      // keeps the matrix cores and HBM busy for exactly the table's time, so
+      // DVFS or contention changes how much work is done, not how long).
+      deadline_task(s, d, sync, false);
+    }
   }
 
   void set_task_timers(TimerSet* t) override {
@@ -517,24 +413,7 @@ class GpuCompute : public ComputeEngine {
       j["programs"] = programs_launched_;
       j["program_tasks"] = program_tasks_;
     }
-    if (mode_ == ComputeMode::Hbm) {
-      // what the streaming tasks moved so far (device totals: every launch and
-      // every replay of a captured one adds to them) in the time they ran
-      uint64_t v[2] = {0, 0};
-      auto st = dev_.create_stream(false);
-      dev_.copy_async(v, hbm_totals_.data(), sizeof(v), *st);
-      st->synchronize();
-      Json h = Json::object();
-      h["working_set_bytes"] = static_cast<double>(3 * hbm_bytes_);
-      h["chunk_bytes"] = static_cast<double>(kernels::kHbmChunkBytes);
-      h["grid"] = grid_;
-      const double bytes = 3.0 * static_cast<double>(kernels::kHbmChunkBytes) * static_cast<double>(v[0]);
-      const double busy = static_cast<double>(v[1]) / hz();
-      h["bytes_moved"] = bytes;
-      h["busy_s"] = busy;
-      h["GBps"] = busy > 0 ? bytes / busy / 1e9 : 0.0;
-      j["hbm"] = h;
-    }
+    if (mode_ == ComputeMode::Hbm) j["hbm"] = hbm_.report(dev_, grid_, hz());
     if (gemm_mode()) {
       j["gemm_dtype"] = dtype_name(dtype_);
       j["gemm_N"] = N_;
@@ -572,6 +451,40 @@ class GpuCompute : public ComputeEngine {
     return hz_;
   }
 
+  // The words every task's sync carries (the builders' gate-only and join
+  // tasks start from an empty sync).
+  kernels::DlSync base_sync(kernels::DlSync sync = {}) const {
+    sync.iter = dev_.iter_word();
+    sync.counters = counters_.as<uint64_t>();
+    sync.gate_timeout = gate_timeout_ticks_;
+    sync.abort = dev_.abort_word();
+    return sync;
+  }
+  // A task's start stamps: `start`, else a slot of the stall timers, and the
+  // slot set_next_start_slot left.
+  void take_start_slots(Stream& s, kernels::DlSync& sync, uint64_t* start) {
+    if (stall_timers_ && !start) start = fixed_ ? stall_timers_->slot() : stall_timers_->task_slot(s);
+    sync.tstart[0] = start;
+    sync.tstart[1] = extra_start_;
+    extra_start_ = nullptr;
+  }
+  // One-wave waits for a task's gates on s, before the launch that starts with it.
+  void wait_gates(Stream& s, const kernels::DlSync& sync) {
+    for (int i = 0; i < 2; ++i)
+      if (sync.gate[i])
+        kernels::gate_wait(sync.gate[i], dev_.iter_word(), sync.tag[i], gate_timeout_ticks_,
+                           counters_.as<uint64_t>() + kernels::kWaitTimeouts, s.native(), dev_.abort_word());
+  }
+  // t joins the program open on s (launched with it: end_program); false:
+  // none is open and the task is a launch of its own.
+  bool add_to_program(Stream& s, const kernels::DlTask& t, bool done_folded) {
+    auto it = programs_.find(&s);
+    if (it == programs_.end() || !it->second.prog.open()) return false;
+    DLNB_REQUIRE(done_folded, "a program task's done event needs gate events");
+    it->second.prog.append(t);
+    return true;
+  }
+
   // Where a task list goes: captured into a graph, the device ring (written
   // by after_capture, before the first replay); launched at once, the
   // host-mapped ring (the kernel reads it where the host wrote it).
@@ -604,28 +517,17 @@ class GpuCompute : public ComputeEngine {
   void deadline_task(Stream& s, double d, kernels::DlSync sync, bool chain, Event* done = nullptr) {
     uint64_t* slot = slot_for(s);
     sync.chain = chain ? absorb_ticks_ : 0u;
-    sync.counters = counters_.as<uint64_t>();
-    sync.iter = dev_.iter_word();
-    sync.gate_timeout = gate_timeout_ticks_;
-    sync.abort = dev_.abort_word();
+    sync = base_sync(sync);
     uint64_t* dgate = nullptr;
     uint32_t dtag = 0;
     const bool folded = done && dev_.arm_gate_record(*done, s, &dgate, &dtag);
     const uint64_t total = ticks(d);
-    auto pit = programs_.find(&s);
-    if (pit != programs_.end() && pit->second.open) {
-      // a task of the open program: launched with it (end_program)
-      DLNB_REQUIRE(folded || !done, "a program task's done event needs gate events");
-      kernels::DlTask t;
-      t.sync = sync;
-      t.sync.done_gate = dgate;
-      t.sync.done_tag = dtag;
-      t.ticks = total;
-      take_pending(s, pit->second, t.sync);
-      DLNB_REQUIRE(pit->second.index < 4096, "more than 4096 program tasks per iteration on one stream");
-      t.epoch = pit->second.index++;  // the kernel derives the epoch from it and the iteration word
-      pit->second.tasks.push_back(t);
-      pit->second.done_free = t.sync.done_gate == nullptr;
+    kernels::DlTask t;
+    t.sync = sync;
+    t.sync.done_gate = dgate;
+    t.sync.done_tag = dtag;
+    t.ticks = total;
+    if (add_to_program(s, t, folded || !done)) {
       chain_live_[slot] = true;
       return;
     }
@@ -645,6 +547,16 @@ class GpuCompute : public ComputeEngine {
     }
     if (done && !folded) s.record(*done);
     chain_live_[slot] = true;
+  }
+
+  // A chained / gated deadline task with its start stamps, reported to the
+  // lane statistics and the stall timers.
+  void noted_deadline_task(Stream& s, double d, kernels::DlSync sync, uint64_t* start, bool chain, Event* done) {
+    note_task(s, d);
+    take_start_slots(s, sync, start);
+    StartNote note{stall_timers_, s, sync.tstart[0], ticks(d), nullptr};
+    deadline_task(s, d, sync, chain, done);
+    if (chain) ++chained_;
   }
 
   // A launch epoch of its own: 32768..65534 (never 0: a fresh slot reads as
@@ -682,41 +594,24 @@ class GpuCompute : public ComputeEngine {
   void fixed_task(Stream& s, double us, double flops, uint64_t* start, kernels::DlSync sync, Event* done) {
     const FixedWork w = size_work(us, flops);
     note_task(s, w.us);
-    if (stall_timers_ && !start) start = stall_timers_->slot();
+    take_start_slots(s, sync, start);
+    start = sync.tstart[0];
     uint64_t* end = stall_timers_ ? stall_timers_->slot() : nullptr;
-    sync.tstart[0] = start;
-    sync.tstart[1] = extra_start_;
-    extra_start_ = nullptr;
-    sync.counters = counters_.as<uint64_t>();
-    sync.iter = dev_.iter_word();
-    sync.gate_timeout = gate_timeout_ticks_;
-    sync.abort = dev_.abort_word();
+    sync = base_sync(sync);
     uint64_t* dgate = nullptr;
     uint32_t dtag = 0;
     const bool folded = done && dev_.arm_gate_record(*done, s, &dgate, &dtag);
-    sync.done_gate = dgate;
-    sync.done_tag = dtag;
     kernels::DlTask t;
     t.sync = sync;
-    t.ticks = 0;
+    t.sync.done_gate = dgate;
+    t.sync.done_tag = dtag;
     t.work_rounds = w.rounds;
     t.tail_kt = w.tail_kt;
     t.tend = end;
-    auto pit = programs_.find(&s);
-    if (pit != programs_.end() && pit->second.open) {
-      DLNB_REQUIRE(folded || !done, "a program task's done event needs gate events");
-      take_pending(s, pit->second, t.sync);
-      DLNB_REQUIRE(pit->second.index < 4096, "more than 4096 program tasks per iteration on one stream");
-      t.epoch = pit->second.index++;
-      pit->second.tasks.push_back(t);
-      pit->second.done_free = t.sync.done_gate == nullptr;
-    } else {
+    if (!add_to_program(s, t, folded || !done)) {
       // a launch of its own (a one-task program with an epoch of its own):
       // the gates' one-wave waits first, as for a program's first task
-      for (int i = 0; i < 2; ++i)
-        if (t.sync.gate[i])
-          kernels::gate_wait(t.sync.gate[i], dev_.iter_word(), t.sync.tag[i], gate_timeout_ticks_,
-                             counters_.as<uint64_t>() + kernels::kWaitTimeouts, s.native(), dev_.abort_word());
+      wait_gates(s, t.sync);
       uint64_t* slot = slot_for(s);
       const kernels::DlTask* dst = place_tasks(s, {t});
       kernels::gemm_tn_deadline_program(A_.data(), B_.data(), C_.data(), kMmax, N_, K_, dtype_, dst, 1, slot, grid_,
@@ -745,6 +640,78 @@ class GpuCompute : public ComputeEngine {
     return slots_.as<uint64_t>() + idx * 8;  // one 64-B line per stream
   }
 
+  // ---- the constructor's steps
+  // What this engine's buffers may take beside the strategy's: 1/8 of this
+  // rank's share of free memory (ranks sharing the GPU each allocate their own set).
+  double memory_share(const ComputeShape& shape) const {
+    return static_cast<double>(dev_.free_memory()) / std::max(1, shape.ranks_on_device) / 8.0;
+  }
+  // The CUs a persistent grid takes: all but comm_cus; split: this rank's
+  // part of them where ranks share the device.
+  int free_cus(const ComputeShape& shape, bool split) const {
+    const int free = std::max(1, cus_ - std::max(0, shape.comm_cus));
+    return split ? std::max(1, free / std::max(1, shape.ranks_on_device)) : free;
+  }
+  // The stand-in is the layer's FFN down projection, C[tokens, hidden] =
+  // A[tokens, ffn] . W[hidden, ffn]^T: its long K (the FFN width) keeps
+  // the per-tile pipeline fill / drain of the persistent kernel small. At
+  // the up-projection shape used before (K = hidden) the deadline kernel did
+  // 0.725 -> 0.787 less MFMA busy per clock on its CUs (bf16 llama3_8b) and
+  // 1810 vs 2672 TF/s (fp8 ViT-H, K = 1280) (profiles/deadline_shapes_r3.md).
+  void choose_shape(const ComputeShape& shape) {
+    // K: a multiple of 128 (bf16: an even K-tile count, the balanced body) or
+    // 256 bytes (fp8: the one-wave-per-SIMD MX kernel).
+    const int kmul = dtype_ == DType::FP8_E4M3 ? 256 : 128;
+    K_ = std::min(65536, std::max(512, (shape.ffn + kmul - 1) / kmul * kmul));
+    N_ = std::min(32768, std::max(1024, (shape.hidden + 255) / 256 * 256));
+    if (!gemm_mode()) return;
+    // The operands must fit beside the strategy's buffers (memory_share).
+    // Large-FFN models (K = ffn up to 64 Ki) shrink K, keeping its multiple
+    // (ffn 53248 x hidden 16384 is ~2.6 GB per rank).
+    const size_t esz = dtype_size(dtype_);
+    const double share = memory_share(shape);
+    auto bytes = [&](int k) { return static_cast<double>(kMmax + N_) * k * esz + static_cast<double>(kMmax) * N_ * 2; };
+    while (K_ > 512 && share > 0 && bytes(K_) > share) K_ = std::max(512, (K_ / 2 + kmul - 1) / kmul * kmul);
+  }
+  // Slots, counters, the programs' task-list rings and the grid of the
+  // deadline and fixed-work kernels.
+  void setup_deadline_state(const ComputeShape& shape) {
+    // one 64-byte line per compute stream; the counters (DlCounter)
+    slots_ = dev_.alloc(kSlots * 64);
+    counters_ = dev_.alloc(kernels::kNumCounters * sizeof(uint64_t));
+    // compute programs' task lists: a device ring (lists captured into a
+    // graph, uploaded after the capture) and a host-mapped ring (lists
+    // launched at once: written by the host, read by the kernel, no copy)
+    prog_dev_ = dev_.alloc(kProgTasks * sizeof(kernels::DlTask));
+    prog_host_ = reinterpret_cast<kernels::DlTask*>(dev_.alloc_stamps(kProgTasks * sizeof(kernels::DlTask) / 8));
+    auto zs = dev_.create_stream(false);
+    dev_.memset_async(slots_.data(), 0, kSlots * 64, *zs);
+    dev_.memset_async(counters_.data(), 0, kernels::kNumCounters * sizeof(uint64_t), *zs);
+    zs->synchronize();
+    // Leave `comm_cus` CUs to collectives: one 128-KiB-LDS block fits per
+    // CU, so a grid of CUs - comm_cus blocks never touches those CUs and
+    // RCCL / copy kernels on the high-priority comm streams always find
+    // room (with the whole chip taken, a comm kernel only starts at a
+    // compute boundary, and overlap collapses).
+    // Fixed work waits for every block of its grid between two tasks, so
+    // ranks sharing the device split the free CUs: all their grids must be
+    // resident at once.
+    grid_ = free_cus(shape, fixed_);
+  }
+  // One launch per task by default. Cutting a task into relaunched
+  // slices (DLNB_GEMM_SLICE_US > 0) was meant to give collectives CUs at
+  // slice boundaries, which the comm_cus reservation already does; at
+  // 500-us slices every slice also abandons a partial 256 x 256 tile and
+  // pays a prologue: 630 vs 679 TF/s per GHz on the headline
+  // (profiles/slice_ab_r3.md), and a 4x larger graph.
+  // Ranks sharing one GPU (loopback, -d 0,0) keep 500-us slices: with one
+  // launch per task a rank's persistent grid holds the CUs for its whole
+  // task and the other ranks' compute (and so the collectives that wait
+  // for it) serialises behind it - 8 loopback ranks of the llama3_8b FSDP
+  // config ran 459 vs 317 ms per iteration (profiles/loopback_w8_r3.md).
+  static double choose_slice_us(const ComputeShape& shape) {
+    return static_cast<double>(env_int("DLNB_GEMM_SLICE_US", shape.ranks_on_device > 1 ? 500 : 0));
+  }
   void alloc_operands() {
     const int Mmax = kMmax;
     const size_t esz = dtype_size(dtype_);
@@ -759,26 +726,30 @@ class GpuCompute : public ComputeEngine {
     s->synchronize();
   }
 
+  // DLNB_FIXED_WORK_CAL="round_us:ktile_us" reuses an earlier calibration
+  // (the report's compute.fixed_work) instead of measuring: a fixed-work run
+  // beside other jobs (tools/interference.py) must do the work it would do
+  // alone, not what a contended calibration says fits the table time.
+  bool calibration_given() {
+    const std::string given = env_or("DLNB_FIXED_WORK_CAL", "");
+    if (given.empty()) return false;
+    const auto kv = split(trim(given), ':');
+    DLNB_REQUIRE(kv.size() == 2, "DLNB_FIXED_WORK_CAL: expected round_us:ktile_us, got '" << given << "'");
+    cal_.round_us = std::stod(kv[0]);
+    cal_.ktile_us = std::stod(kv[1]);
+    DLNB_REQUIRE(cal_.round_us > 0 && cal_.ktile_us > 0, "DLNB_FIXED_WORK_CAL: bad values '" << given << "'");
+    cal_given_ = true;
+    return true;
+  }
   // Fixed work's unit costs with nothing else running: one-task programs of
   // R full-K rounds (R = 20 and 60: the difference removes the launch and
   // the first tile's ramp) and of a tail of nk / 2 K-tiles after one round.
   void calibrate() {
+    DLNB_REQUIRE(kernels::deadline_program_ok(kMmax, N_, K_, dtype_),
+                 "fixed-work compute: no program kernel for the stand-in shape " << kMmax << "x" << N_ << "x" << K_);
     nk_ = kernels::program_ktiles(kMmax, N_, K_, dtype_);
     tail_mul_ = static_cast<uint32_t>(std::max(1, kernels::program_tail_multiple(kMmax, N_, K_, dtype_)));
-    // DLNB_FIXED_WORK_CAL="round_us:ktile_us" reuses an earlier calibration
-    // (the report's compute.fixed_work) instead of measuring: a fixed-work run
-    // beside other jobs (tools/interference.py) must do the work it would do
-    // alone, not what a contended calibration says fits the table time.
-    const std::string given = env_or("DLNB_FIXED_WORK_CAL", "");
-    if (!given.empty()) {
-      const auto kv = split(trim(given), ':');
-      DLNB_REQUIRE(kv.size() == 2, "DLNB_FIXED_WORK_CAL: expected round_us:ktile_us, got '" << given << "'");
-      cal_.round_us = std::stod(kv[0]);
-      cal_.ktile_us = std::stod(kv[1]);
-      DLNB_REQUIRE(cal_.round_us > 0 && cal_.ktile_us > 0, "DLNB_FIXED_WORK_CAL: bad values '" << given << "'");
-      cal_given_ = true;
-      return;
-    }
+    if (calibration_given()) return;
     auto s = dev_.create_stream(false);
     auto e0 = dev_.create_event(true);
     auto e1 = dev_.create_event(true);
@@ -829,119 +800,24 @@ class GpuCompute : public ComputeEngine {
   bool fixed_ = false;
   Buffer slots_;
   Buffer counters_;  // kernels::DlCounter words (DlSync::counters)
-  // programs: the open task list per stream, the device ring their task lists
+  // programs: the task list builder per stream (it takes the stream's gate
+  // events while open: Device::StreamFold), the device ring their task lists
   // live in, uploads deferred past a graph capture
-  struct Fold : Device::StreamFold {
-    GpuCompute* e = nullptr;
-    Stream* s = nullptr;
-    void fold_wait(const uint64_t* gate, uint32_t tag) override { e->fold_wait(*s, gate, tag); }
-    void fold_record(Event& ev) override { e->fold_record(*s, ev); }
+  struct Lane : Device::StreamFold {
+    Lane(GpuCompute& e, Stream& s) : prog([&e] { return e.base_sync(); }, e.fixed_), e(e), s(s) {}
+    void fold_wait(const uint64_t* gate, uint32_t tag) override { prog.fold_wait(gate, tag); }
+    void fold_record(Event& ev) override {
+      uint64_t* g = nullptr;
+      uint32_t tag = 0;
+      DLNB_REQUIRE(e.dev_.arm_gate_record(ev, s, &g, &tag), "fold_record: not a gate event");
+      prog.fold_record(g, tag);
+    }
+    ProgramBuilder prog;
+    GpuCompute& e;
+    Stream& s;
   };
-  struct Program {
-    bool open = false;
-    uint32_t index = 0;  // program tasks of the iteration so far (DlTask::epoch)
-    std::vector<kernels::DlTask> tasks;
-    // folded gate-event waits (gate, tag) the next task takes as its gates
-    std::vector<std::pair<const uint64_t*, uint32_t>> pending;
-    bool done_free = false;  // tasks.back() has no done gate: a record right after it takes that one
-    bool split = false;      // a short task was launched on its own while the program was open
-    Fold fold;
-  };
-
-  // ---- gate events folded into the open program (Device::StreamFold)
-  void fold_wait(Stream& s, const uint64_t* gate, uint32_t tag) {
-    Program& p = programs_[&s];
-    for (auto& w : p.pending)
-      if (w.first == gate) {  // the same gate again: its latest record
-        w.second = tag;
-        return;
-      }
-    p.pending.emplace_back(gate, tag);
-  }
-  void fold_record(Stream& s, Event& ev) {
-    Program& p = programs_[&s];
-    uint64_t* g = nullptr;
-    uint32_t tag = 0;
-    DLNB_REQUIRE(dev_.arm_gate_record(ev, s, &g, &tag), "fold_record: not a gate event");
-    if (p.pending.empty() && p.done_free && !p.tasks.empty()) {
-      // recorded right after a task: that task's done gate
-      p.tasks.back().sync.done_gate = g;
-      p.tasks.back().sync.done_tag = tag;
-      p.done_free = false;
-      return;
-    }
-    emit_pending(s, p, g, tag);
-    if (p.tasks.empty() || p.tasks.back().sync.done_gate != g) {
-      // nothing pending and no task to carry it: a gate-only task raises it
-      kernels::DlTask t = gate_task();
-      t.sync.done_gate = g;
-      t.sync.done_tag = tag;
-      push_task(p, t);
-    }
-    p.done_free = false;
-  }
-  kernels::DlTask gate_task() const {
-    kernels::DlTask t;
-    t.sync.iter = dev_.iter_word();
-    t.sync.counters = counters_.as<uint64_t>();
-    t.sync.gate_timeout = gate_timeout_ticks_;
-    t.sync.abort = dev_.abort_word();
-    t.ticks = fixed_ ? 0 : 1;  // (deadline: the stream's chain goes on from when its gates opened)
-    t.flags = kernels::kTaskGateOnly;
-    return t;
-  }
-  void push_task(Program& p, const kernels::DlTask& t) {
-    DLNB_REQUIRE(p.index < 4096, "more than 4096 program tasks per iteration on one stream");
-    kernels::DlTask c = t;
-    c.epoch = p.index++;
-    p.tasks.push_back(c);
-  }
-  // The pending waits as gate-only tasks (two gates each); the last one
-  // raises done_gate when given.
-  void emit_pending(Stream& s, Program& p, uint64_t* done_gate, uint32_t done_tag) {
-    (void)s;
-    while (!p.pending.empty()) {
-      kernels::DlTask t = gate_task();
-      for (int i = 0; i < 2 && !p.pending.empty(); ++i) {
-        t.sync.gate[i] = p.pending.front().first;
-        t.sync.tag[i] = p.pending.front().second;
-        p.pending.erase(p.pending.begin());
-      }
-      if (p.pending.empty() && done_gate) {
-        t.sync.done_gate = done_gate;
-        t.sync.done_tag = done_tag;
-      }
-      push_task(p, t);
-      p.done_free = false;
-    }
-  }
-  // A task about to join the program takes the pending waits as its gates
-  // (those beyond its free gate slots go to gate-only tasks before it).
-  void take_pending(Stream& s, Program& p, kernels::DlSync& sync) {
-    if (p.pending.empty()) return;
-    const size_t free_slots = (sync.gate[0] ? 0u : 1u) + (sync.gate[1] ? 0u : 1u);
-    if (p.pending.size() > free_slots) {
-      // keep the last free_slots for the task, the rest before it
-      std::vector<std::pair<const uint64_t*, uint32_t>> keep(p.pending.end() - static_cast<long>(free_slots),
-                                                             p.pending.end());
-      p.pending.resize(p.pending.size() - free_slots);
-      emit_pending(s, p, nullptr, 0);
-      p.pending = keep;
-    }
-    for (int i = 0; i < 2 && !p.pending.empty(); ++i) {
-      if (sync.gate[i]) continue;
-      sync.gate[i] = p.pending.front().first;
-      sync.tag[i] = p.pending.front().second;
-      p.pending.erase(p.pending.begin());
-    }
-  }
-  std::map<Stream*, Program> programs_;
-  struct Join {
-    std::vector<uint64_t*> gates;
-    uint32_t tag;
-    uint64_t* host_done;
-  };
-  std::map<Stream*, Join> joins_;  // set_lane_join, taken by the next end_program
+  std::map<Stream*, Lane> programs_;
+  std::map<Stream*, ProgramJoin> joins_;  // set_lane_join, taken by the next end_program
   std::set<Stream*> joined_;
   std::map<Stream*, long> program_count_;  // programs launched per stream (programs_on)
   Buffer prog_dev_;
@@ -1004,9 +880,8 @@ class GpuCompute : public ComputeEngine {
   uint32_t tail_mul_ = 2;      // the tail's K-tile multiple
   FixedCal cal_;
   bool cal_given_ = false;
-  Buffer A_, B_, C_;  // GEMM operands and product; hbm: the three streamed arrays
-  size_t hbm_bytes_ = 0;  // hbm: bytes per array (a whole number of chunks)
-  Buffer hbm_totals_;     // hbm: {chunks, ticks} the kernels add to (kernels::hbm_stream)
+  Buffer A_, B_, C_;  // GEMM operands and product
+  HbmStream hbm_;
   TimerSet* task_timers_ = nullptr;
 };
 

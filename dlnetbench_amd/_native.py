@@ -77,6 +77,7 @@ def lib() -> ctypes.CDLL:
     L.dlnb_task_size.restype = c_int
     L.dlnb_gemm_program.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(TaskDesc), c_int,
                                     c_vp, c_vp, c_vp, c_dbl, c_int, c_vp, c_vp, c_int, c_vp, ctypes.c_uint]
+    L.dlnb_program_script.argtypes = [ctypes.c_char_p, c_int, ctypes.POINTER(c_vp)]
     L.dlnb_program_ktiles.argtypes = [c_int, c_int, c_int, c_int]
     L.dlnb_host_words.argtypes = [c_int, ctypes.POINTER(c_vp)]
     L.dlnb_host_words.restype = c_vp
@@ -133,6 +134,15 @@ def run_raw(strategy: str, args: List[str]) -> dict:
     out = ctypes.c_void_p()
     check(L.dlnb_run(strategy.encode(), len(args), argv, ctypes.byref(out)))
     return json.loads(_take_string(out)) if out.value else {}
+
+
+def program_script(script: str, fixed_work: bool = False) -> dict:
+    """Drive the compute program builder (csrc/src/program.cpp) from a text
+    script (ops: csrc/src/capi.cpp dlnb_program_script); no GPU needed.
+    Returns {"launches": [[task, ...], ...], "joined": bool}."""
+    out = ctypes.c_void_p()
+    check(lib().dlnb_program_script(script.encode(), int(fixed_work), ctypes.byref(out)))
+    return json.loads(_take_string(out))
 
 
 def parse_stats(path: str) -> dict:
