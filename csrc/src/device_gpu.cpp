@@ -69,8 +69,17 @@ class GpuStream : public Stream {
     DLNB_HIP_CHECK(hipSetDevice(device));
     int lo = 0, hi = 0;
     DLNB_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    // hi is the numerically smallest (= greatest) priority.
-    DLNB_HIP_CHECK(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, high_priority ? hi : lo));
+    // hi is the numerically smallest (= greatest) priority. The compute lane
+    // takes the low-priority pool, so it shares no hardware queue with the
+    // comm lanes (high) or the process's other streams (default) - but only
+    // in a CLI process, which ends with its job. A library host (Python)
+    // lives on: one that had once created low-priority streams slowed every
+    // later process on the device until it exited (the comm-bound DP step 3 ms
+    // over its floor instead of 0.09, profiles/host_stream_priority.md).
+    // There the compute lane has the default priority; default and high
+    // priority streams leave nothing behind.
+    const int compute = cli_process() ? lo : 0;
+    DLNB_HIP_CHECK(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, high_priority ? hi : compute));
     std::lock_guard<std::mutex> g(set_->mu);
     set_->live.insert(s);
   }
