@@ -31,6 +31,13 @@
 //           compute.hbm.GBps beside collectives against the same run alone is
 //           an HBM-contention reading that needs no calibration. One kernel
 //           per task like spin (no gates, no programs); sleep on the CPU device.
+//   attn  - the attention core: a fused flash-attention forward kernel (two
+//           dependent MFMA products with an online softmax between them, K / V
+//           tiles re-read from LDS by every wave, HBM traffic only Q, K, V in
+//           and O out) over a causal sequence shaped from the model, repeated
+//           until the table's deadline on the same CU budget, counting its
+//           KV-tile steps; the report's compute.attn.TFLOPs is the rate it
+//           reached. hbm's paths; sleep on the CPU device.
 #pragma once
 
 #include <memory>
@@ -43,7 +50,7 @@
 
 namespace dlnb {
 
-enum class ComputeMode { Sleep, Spin, Gemm, GemmWork, Flops, Hbm };
+enum class ComputeMode { Sleep, Spin, Gemm, GemmWork, Flops, Hbm, Attn };
 
 ComputeMode parse_compute_mode(const std::string& s, DeviceKind dev);
 const char* compute_mode_name(ComputeMode m);
@@ -51,6 +58,9 @@ const char* compute_mode_name(ComputeMode m);
 struct ComputeShape {
   int hidden = 4096;  // model hidden size (N of the stand-in GEMM: the FFN down projection)
   int ffn = 16384;    // FFN width (K)
+  int heads = 0;      // attn: query heads (0: hidden / 128)
+  int kv_heads = 0;   // attn: K / V heads (0 or not dividing heads: = heads)
+  int seq = 0;        // attn: sequence length (0: 4096)
   DType dtype = DType::BF16;
   int comm_cus = 32;  // CUs the persistent compute leaves to collectives
   // Ranks sharing the device (loopback rank threads, several processes on one

@@ -11,6 +11,9 @@
 //   * busy_spin         - every CU runs dependent FMAs until a deadline
 //   * hbm_stream        - one block per CU streams c = a + b (bf16) through
 //                          HBM, once or until a deadline, and counts its bytes
+//   * attention_fwd     - flash-attention forward, bf16, head dim 128, GQA and
+//                          causal: two MFMA products with a register-resident
+//                          online softmax, once or until a deadline
 //   * gemm_tn           - C[M,N] (bf16) = A[M,K] · B[N,K]^T, MFMA 16x16x32
 //                          bf16 or OCP-fp8 e4m3 operands, 256x256 tiles,
 //                          global_load_lds staging into an XOR-swizzled LDS
@@ -149,6 +152,31 @@ constexpr size_t kHbmChunkBytes = 64 * 1024;
 void hbm_stream(const void* a, const void* b, void* c, size_t n, uint64_t ticks, int grid, void* stream,
                 uint64_t* start = nullptr, uint64_t* start2 = nullptr, uint64_t* totals = nullptr /* {chunks, ticks} */,
                 uint64_t* per_block = nullptr);
+// Fused attention forward (attention.hip): O[b,h] = softmax(scale Q[b,h] K[b,g]^T
+// (+ causal mask)) V[b,g], g = h / (H / Hkv); bf16 in and out, fp32 scores,
+// softmax and accumulation; neither S nor P touches global memory.
+//   q, o: [B, H, Sq, 128]; k, v: [B, Hkv, Skv, 128]; contiguous, 16-byte
+//   aligned; H % Hkv == 0, Sq % 128 == 0, Skv % kAttnKvTile == 0, scale > 0;
+//   causal (key j visible to query i iff j <= i) needs Sq == Skv.
+//   lse (optional): [B, H, Sq] fp32, ln of the sum of exp(scaled scores).
+// A persistent grid of `grid` 256-thread blocks, one per CU (0: every CU; at
+// most the CUs). The work item is one (b, h, 128-row Q tile); block blk takes
+// items blk, blk + grid, ... and walks each item's KV tiles of kAttnKvTile keys
+// (tiles wholly above the causal diagonal are skipped).
+//   ticks == 0: one shot, every item exactly once.
+//   ticks > 0: the sequence wraps round; a block reads the clock once per
+//     item and leaves after the item in hand once `ticks` have passed since it
+//     entered the kernel. start / start2 as busy_spin's.
+// Accounting (optional; device memory the kernel adds to, so replays of a
+// captured launch accumulate): totals[0] += KV-tile steps of the grid, each
+// 4 * 128 * kAttnKvTile * 128 FLOPs; totals[1] += ticks (once per launch);
+// per_block[blk] = the block's steps. Anything outside the limits throws
+// before a launch.
+constexpr int kAttnKvTile = 128;
+void attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv, int Sq,
+                   int Skv, float scale, bool causal, uint64_t ticks, int grid, void* stream, uint64_t* start = nullptr,
+                   uint64_t* start2 = nullptr, uint64_t* totals = nullptr /* {KV-tile steps, ticks} */,
+                   uint64_t* per_block = nullptr);
 // The deadline clock's rate in Hz: measured against the host's steady clock
 // once per process (clock_cal_begin starts the window - the GPU device does
 // at creation - and the first wallclock_hz call ends it, sleeping until

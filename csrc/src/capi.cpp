@@ -346,6 +346,26 @@ int dlnb_hbm_stream(const void* a, const void* b, void* c, size_t n, double us, 
 
 size_t dlnb_hbm_chunk_bytes() { return dlnb::kernels::kHbmChunkBytes; }
 
+// Attention forward (kernels::attention_fwd) over bf16 q, o [B, H, Sq, 128] and
+// k, v [B, Hkv, Skv, 128]: us = 0 computes every Q tile once, us > 0 keeps
+// recomputing them for that long. lse (fp32 [B, H, Sq]), start, totals (two
+// device words {KV-tile steps, ticks} the kernel adds to) and per_block (grid
+// device words) are optional. grid 0 = every CU.
+int dlnb_attention_fwd(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H, int Hkv, int Sq,
+                       int Skv, float scale, int causal, double us, int device, int grid, void* stream, void* start,
+                       void* totals, void* per_block) {
+  return guard([&] {
+    DLNB_REQUIRE(us >= 0, "dlnb_attention_fwd: negative duration");
+    uint64_t ticks = 0;
+    if (us > 0) ticks = std::max<uint64_t>(1, static_cast<uint64_t>(us * 1e-6 * dlnb::kernels::wallclock_hz(device) + 0.5));
+    dlnb::kernels::attention_fwd(q, k, v, o, static_cast<float*>(lse), B, H, Hkv, Sq, Skv, scale, causal != 0, ticks,
+                                 grid, stream, static_cast<uint64_t*>(start), nullptr, static_cast<uint64_t*>(totals),
+                                 static_cast<uint64_t*>(per_block));
+  });
+}
+
+int dlnb_attn_kv_tile() { return dlnb::kernels::kAttnKvTile; }
+
 int dlnb_sgd_momentum_bf16(void* p, void* m, const void* g, size_t n, float lr, float beta, void* stream) {
   return guard([&] { dlnb::kernels::sgd_momentum_bf16(p, m, g, n, lr, beta, stream); });
 }

@@ -20,7 +20,8 @@ ComputeMode parse_compute_mode(const std::string& s, DeviceKind dev) {
   if (s == "gemm-work" || s == "gemm_work") return ComputeMode::GemmWork;
   if (s == "flops") return ComputeMode::Flops;
   if (s == "hbm") return ComputeMode::Hbm;
-  DLNB_THROW("unknown compute mode '" << s << "' (auto, sleep, spin, gemm, gemm-work, flops, hbm)");
+  if (s == "attn") return ComputeMode::Attn;
+  DLNB_THROW("unknown compute mode '" << s << "' (auto, sleep, spin, gemm, gemm-work, flops, hbm, attn)");
 }
 
 const char* compute_mode_name(ComputeMode m) {
@@ -31,6 +32,7 @@ const char* compute_mode_name(ComputeMode m) {
     case ComputeMode::GemmWork: return "gemm-work";
     case ComputeMode::Flops: return "flops";
     case ComputeMode::Hbm: return "hbm";
+    case ComputeMode::Attn: return "attn";
   }
   return "?";
 }
@@ -52,7 +54,7 @@ class CpuCompute : public ComputeEngine {
         while (now_s() < end) x = x * 1.0000001 + 1e-9;
       });
     } else {
-      // sleep; gemm/flops/hbm have no CPU implementation and fall back to sleep.
+      // sleep; gemm/flops/hbm/attn have no CPU implementation and fall back to sleep.
       dev_.host_task(s, [d] { precise_sleep_us(d); });
     }
   }
@@ -136,6 +138,74 @@ struct HbmStream {
   }
 };
 
+// The attn mode's tensors, launches and report block: causal self-attention of
+// one sequence (B = 1) shaped from the model.
+struct AttnStandIn {
+  static constexpr int kHeadDim = 128;
+  Buffer q, k, v, o;
+  Buffer totals;  // {KV-tile steps, ticks} the kernels add to (kernels::attention_fwd)
+  int heads = 1, kv_heads = 1, seq = 4096;
+  float scale = 0.0f;
+
+  size_t q_bytes() const { return static_cast<size_t>(heads) * seq * kHeadDim * 2; }
+  size_t kv_bytes() const { return static_cast<size_t>(kv_heads) * seq * kHeadDim * 2; }
+
+  // H = hidden / 128 heads of dimension 128; Hkv from the architecture when it
+  // divides H; S = the architecture's sequence rounded down to 128 within
+  // [1024, 8192] (4096 when unknown), halved while Q + K + V + O exceed `share`
+  // bytes (the GEMM operands' rule).
+  void setup(Device& dev, const ComputeShape& shape, double share) {
+    heads = shape.heads > 0 ? shape.heads : std::max(1, shape.hidden / kHeadDim);
+    kv_heads = shape.kv_heads > 0 && heads % shape.kv_heads == 0 ? shape.kv_heads : heads;
+    seq = shape.seq > 0 ? std::min(8192, std::max(1024, shape.seq / 128 * 128)) : 4096;
+    while (seq > 128 && share > 0 && 2.0 * static_cast<double>(q_bytes() + kv_bytes()) > share) seq = seq / 2 / 128 * 128;
+    scale = 1.0f / std::sqrt(static_cast<float>(kHeadDim));
+    q = dev.alloc(q_bytes());
+    o = dev.alloc(q_bytes());
+    k = dev.alloc(kv_bytes());
+    v = dev.alloc(kv_bytes());
+    totals = dev.alloc(2 * sizeof(uint64_t));
+    auto s = dev.create_stream(false);
+    dev.fill_random(q.data(), q_bytes() / 2, DType::BF16, 1, *s);
+    dev.fill_random(k.data(), kv_bytes() / 2, DType::BF16, 2, *s);
+    dev.fill_random(v.data(), kv_bytes() / 2, DType::BF16, 3, *s);
+    dev.memset_async(totals.data(), 0, 2 * sizeof(uint64_t), *s);
+    // the kernel's first launch (code object load, the one-block-per-CU
+    // check) here, never inside a graph capture: one Q tile, counted nowhere
+    kernels::attention_fwd(q.data(), k.data(), v.data(), o.data(), nullptr, 1, 1, 1, 128, 128, scale, true, 0, 1,
+                           s->native());
+    s->synchronize();
+  }
+  void task(Stream& s, uint64_t ticks, int grid, uint64_t* start, uint64_t* extra) {
+    kernels::attention_fwd(q.data(), k.data(), v.data(), o.data(), nullptr, 1, heads, kv_heads, seq, seq, scale, true,
+                           std::max<uint64_t>(ticks, 1), grid, s.native(), start, extra, totals.as<uint64_t>(), nullptr);
+  }
+  // What the attention tasks computed so far (device totals: every launch and
+  // every replay of a captured one adds to them) in the time they ran. A
+  // KV-tile step is a fixed amount of work, so the rate is exact under the
+  // causal mode's skipped tiles.
+  Json report(Device& dev, int grid, double hz) const {
+    uint64_t t[2] = {0, 0};
+    auto st = dev.create_stream(false);
+    dev.copy_async(t, totals.data(), sizeof(t), *st);
+    st->synchronize();
+    Json a = Json::object();
+    a["seq"] = seq;
+    a["heads"] = heads;
+    a["kv_heads"] = kv_heads;
+    a["head_dim"] = kHeadDim;
+    a["causal"] = true;
+    a["grid"] = grid;
+    a["kv_tile"] = kernels::kAttnKvTile;
+    const double flops = 4.0 * 128 * kernels::kAttnKvTile * kHeadDim * static_cast<double>(t[0]);
+    const double busy = static_cast<double>(t[1]) / hz;
+    a["kv_tile_steps"] = static_cast<double>(t[0]);
+    a["busy_s"] = busy;
+    a["TFLOPs"] = busy > 0 ? flops / busy / 1e12 : 0.0;
+    return a;
+  }
+};
+
 class GpuCompute : public ComputeEngine {
  public:
   GpuCompute(Device& dev, ComputeMode mode, const ComputeShape& shape, double scale)
@@ -158,6 +228,11 @@ class GpuCompute : public ComputeEngine {
       // deadline from there, and the task would last up to twice the table's time.
       grid_ = free_cus(shape, true);
       hbm_.setup(dev_, memory_share(shape));
+    }
+    if (mode_ == ComputeMode::Attn) {
+      // one block per CU too (attention.hip): hbm's grid rule
+      grid_ = free_cus(shape, true);
+      attn_.setup(dev_, shape, memory_share(shape));
     }
     if (gemm_mode()) setup_deadline_state(shape);
     slice_us_ = mode_ == ComputeMode::Gemm ? choose_slice_us(shape) : 0.0;
@@ -373,6 +448,8 @@ class GpuCompute : public ComputeEngine {
       kernels::busy_spin(ticks(d), cus_, s.native(), t0, t1);
     } else if (mode_ == ComputeMode::Hbm) {
       hbm_.task(s, ticks(d), grid_, t0, t1);
+    } else if (mode_ == ComputeMode::Attn) {
+      attn_.task(s, ticks(d), grid_, t0, t1);
     } else {
       // Fixed duration, real MFMA work: persistent deadline GEMM (the stand-in
       // keeps the matrix cores and HBM busy for exactly the table's time, so
@@ -414,6 +491,7 @@ class GpuCompute : public ComputeEngine {
       j["program_tasks"] = program_tasks_;
     }
     if (mode_ == ComputeMode::Hbm) j["hbm"] = hbm_.report(dev_, grid_, hz());
+    if (mode_ == ComputeMode::Attn) j["attn"] = attn_.report(dev_, grid_, hz());
     if (gemm_mode()) {
       j["gemm_dtype"] = dtype_name(dtype_);
       j["gemm_N"] = N_;
@@ -882,6 +960,7 @@ class GpuCompute : public ComputeEngine {
   bool cal_given_ = false;
   Buffer A_, B_, C_;  // GEMM operands and product
   HbmStream hbm_;
+  AttnStandIn attn_;
   TimerSet* task_timers_ = nullptr;
 };
 

@@ -77,7 +77,8 @@ std::string usage(StrategyKind kind, const std::string& prog) {
      << "  --backend B            auto | rccl | xgmi | mixed | cpu | loopback | loopback-cpu\n"
      << "  --ranks N              loopback: ranks run as threads of this process on one GPU\n"
      << "                         (loopback-cpu: on the CPU device), default 2\n"
-     << "  --compute C            auto | sleep | spin | gemm | gemm-work | flops\n"
+     << "  --compute C            auto | sleep | spin | gemm | gemm-work | flops | hbm | attn\n"
+     << "                         (attn: a fused attention forward kernel shaped from the model, until the deadline)\n"
      << "  --wire-dtype T         bf16 | fp16 | fp32 | fp8 (collective element type)\n"
      << "  --wire-quant Q         none | mxfp8: bf16 collectives are quantized block-wise (MXFP8 E4M3, 32 elements\n"
      << "                         per e8m0 scale) before the transport and dequantized after it (--wire-dtype bf16)\n"

@@ -605,6 +605,14 @@ RunSetup setup_rank(const Options& opt, Context& ctx, std::unique_ptr<Strategy>&
   shape.hidden = static_cast<int>(ctx.stats.embedded_dim);
   uint64_t ffn = ctx.stats.ffn_dim ? ctx.stats.ffn_dim : (ctx.have_arch && ctx.arch.ff_dim ? ctx.arch.ff_dim : 4 * ctx.stats.embedded_dim);
   shape.ffn = static_cast<int>(ffn);
+  // the attn mode's shape: heads of dimension 128, the architecture's KV heads and sequence where known
+  shape.heads = std::max(1, shape.hidden / 128);
+  if (ctx.have_arch) {
+    const Json& raw = ctx.arch.raw;
+    if (raw.is_object() && raw.contains("dlnb") && raw.at("dlnb").is_object() && raw.at("dlnb").contains("num_kv_heads"))
+      shape.kv_heads = static_cast<int>(raw.at("dlnb").at("num_kv_heads").as_int());
+    shape.seq = static_cast<int>(std::min<uint64_t>(ctx.arch.seq_len, 1u << 30));
+  }
   std::string cdt = opt.compute_dtype;
   if (cdt == "auto") cdt = ctx.stats.dtype.find("8") != std::string::npos ? "fp8" : "bf16";
   shape.dtype = parse_dtype(cdt);

@@ -89,6 +89,9 @@ def lib() -> ctypes.CDLL:
     L.dlnb_sgd_momentum_bf16.argtypes = [c_vp, c_vp, c_vp, c_size, c_float, c_float, c_vp]
     L.dlnb_hbm_stream.argtypes = [c_vp, c_vp, c_vp, c_size, c_dbl, c_int, c_int, c_vp, c_vp, c_vp, c_vp]
     L.dlnb_hbm_chunk_bytes.restype = c_size
+    L.dlnb_attention_fwd.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                     c_dbl, c_int, c_int, c_vp, c_vp, c_vp, c_vp]
+    L.dlnb_attn_kv_tile.restype = c_int
     L.dlnb_stamp.argtypes = [c_vp, c_vp]
     L.dlnb_mx_wire_bytes.argtypes = [c_size]
     L.dlnb_mx_wire_bytes.restype = c_size
