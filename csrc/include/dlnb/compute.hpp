@@ -37,7 +37,10 @@
 //           and O out) over a causal sequence shaped from the model, repeated
 //           until the table's deadline on the same CU budget, counting its
 //           KV-tile steps; the report's compute.attn.TFLOPs is the rate it
-//           reached. hbm's paths; sleep on the CPU device.
+//           reached. In the compute dtype, as the GEMM modes: bf16, or for a
+//           float8 model (--compute-dtype fp8) e4m3 Q, K, V on the fp8 MFMA
+//           with a bf16 O (compute.attn.dtype; a step is the same FLOPs in
+//           both). hbm's paths; sleep on the CPU device.
 #pragma once
 
 #include <memory>

@@ -14,6 +14,8 @@
 //   * attention_fwd     - flash-attention forward, bf16, head dim 128, GQA and
 //                          causal: two MFMA products with a register-resident
 //                          online softmax, once or until a deadline
+//   * attention_fwd_fp8 - the same with e4m3 Q, K, V on the 32x32x64 fp8 MFMA,
+//                          P quantized in registers, bf16 out
 //   * gemm_tn           - C[M,N] (bf16) = A[M,K] · B[N,K]^T, MFMA 16x16x32
 //                          bf16 or OCP-fp8 e4m3 operands, 256x256 tiles,
 //                          global_load_lds staging into an XOR-swizzled LDS
@@ -177,6 +179,17 @@ void attention_fwd(const void* q, const void* k, const void* v, void* o, float* 
                    int Skv, float scale, bool causal, uint64_t ticks, int grid, void* stream, uint64_t* start = nullptr,
                    uint64_t* start2 = nullptr, uint64_t* totals = nullptr /* {KV-tile steps, ticks} */,
                    uint64_t* per_block = nullptr);
+// The same in fp8 (attention_fp8.hip): O = v_scale softmax(scale Q K^T (+ causal
+// mask)) V with q, k, v in OCP e4m3 (1 byte, rows of 128 B) and o in bf16;
+// both products on the fp8 MFMA, P quantized to e4m3 in registers as
+// 2^8 exp2(s - max), lse from the unrounded fp32 sum. The caller folds the
+// Q and K descales into scale; v_scale (positive, finite) is V's. Shape
+// contract, grid, ticks, start words and accounting exactly as attention_fwd:
+// a step is kAttnKvTile keys against a 128-row Q tile in both.
+void attention_fwd_fp8(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv, int Sq,
+                       int Skv, float scale, float v_scale, bool causal, uint64_t ticks, int grid, void* stream,
+                       uint64_t* start = nullptr, uint64_t* start2 = nullptr,
+                       uint64_t* totals = nullptr /* {KV-tile steps, ticks} */, uint64_t* per_block = nullptr);
 // The deadline clock's rate in Hz: measured against the host's steady clock
 // once per process (clock_cal_begin starts the window - the GPU device does
 // at creation - and the first wallclock_hz call ends it, sleeping until

@@ -364,6 +364,21 @@ int dlnb_attention_fwd(const void* q, const void* k, const void* v, void* o, voi
   });
 }
 
+// The same over e4m3 q, k, v (1 byte per element) and a bf16 o
+// (kernels::attention_fwd_fp8); v_scale multiplies the result.
+int dlnb_attention_fwd_fp8(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H, int Hkv, int Sq,
+                           int Skv, float scale, float v_scale, int causal, double us, int device, int grid, void* stream,
+                           void* start, void* totals, void* per_block) {
+  return guard([&] {
+    DLNB_REQUIRE(us >= 0, "dlnb_attention_fwd_fp8: negative duration");
+    uint64_t ticks = 0;
+    if (us > 0) ticks = std::max<uint64_t>(1, static_cast<uint64_t>(us * 1e-6 * dlnb::kernels::wallclock_hz(device) + 0.5));
+    dlnb::kernels::attention_fwd_fp8(q, k, v, o, static_cast<float*>(lse), B, H, Hkv, Sq, Skv, scale, v_scale, causal != 0,
+                                     ticks, grid, stream, static_cast<uint64_t*>(start), nullptr,
+                                     static_cast<uint64_t*>(totals), static_cast<uint64_t*>(per_block));
+  });
+}
+
 int dlnb_attn_kv_tile() { return dlnb::kernels::kAttnKvTile; }
 
 int dlnb_sgd_momentum_bf16(void* p, void* m, const void* g, size_t n, float lr, float beta, void* stream) {

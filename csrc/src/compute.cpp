@@ -139,46 +139,59 @@ struct HbmStream {
 };
 
 // The attn mode's tensors, launches and report block: causal self-attention of
-// one sequence (B = 1) shaped from the model.
+// one sequence (B = 1) shaped from the model, in the compute dtype: bf16
+// (attention.hip) or e4m3 Q / K / V with a bf16 O (attention_fp8.hip).
 struct AttnStandIn {
   static constexpr int kHeadDim = 128;
   Buffer q, k, v, o;
-  Buffer totals;  // {KV-tile steps, ticks} the kernels add to (kernels::attention_fwd)
+  Buffer totals;  // {KV-tile steps, ticks} the kernels add to (kernels::attention_fwd, attention_fwd_fp8)
   int heads = 1, kv_heads = 1, seq = 4096;
   float scale = 0.0f;
+  DType dtype = DType::BF16;  // of Q, K and V
 
-  size_t q_bytes() const { return static_cast<size_t>(heads) * seq * kHeadDim * 2; }
-  size_t kv_bytes() const { return static_cast<size_t>(kv_heads) * seq * kHeadDim * 2; }
+  size_t q_count() const { return static_cast<size_t>(heads) * seq * kHeadDim; }
+  size_t kv_count() const { return static_cast<size_t>(kv_heads) * seq * kHeadDim; }
+  size_t q_bytes() const { return q_count() * dtype_size(dtype); }
+  size_t kv_bytes() const { return kv_count() * dtype_size(dtype); }
+  size_t o_bytes() const { return q_count() * 2; }
+  void launch(int H, int Hkv, int S, uint64_t ticks, int grid, void* stream, uint64_t* start, uint64_t* extra,
+              uint64_t* tot) {
+    if (dtype == DType::FP8_E4M3)
+      kernels::attention_fwd_fp8(q.data(), k.data(), v.data(), o.data(), nullptr, 1, H, Hkv, S, S, scale, 1.0f, true,
+                                 ticks, grid, stream, start, extra, tot, nullptr);
+    else
+      kernels::attention_fwd(q.data(), k.data(), v.data(), o.data(), nullptr, 1, H, Hkv, S, S, scale, true, ticks, grid,
+                             stream, start, extra, tot, nullptr);
+  }
 
   // H = hidden / 128 heads of dimension 128; Hkv from the architecture when it
   // divides H; S = the architecture's sequence rounded down to 128 within
   // [1024, 8192] (4096 when unknown), halved while Q + K + V + O exceed `share`
   // bytes (the GEMM operands' rule).
-  void setup(Device& dev, const ComputeShape& shape, double share) {
+  void setup(Device& dev, const ComputeShape& shape, DType dt, double share) {
+    dtype = dt;
     heads = shape.heads > 0 ? shape.heads : std::max(1, shape.hidden / kHeadDim);
     kv_heads = shape.kv_heads > 0 && heads % shape.kv_heads == 0 ? shape.kv_heads : heads;
     seq = shape.seq > 0 ? std::min(8192, std::max(1024, shape.seq / 128 * 128)) : 4096;
-    while (seq > 128 && share > 0 && 2.0 * static_cast<double>(q_bytes() + kv_bytes()) > share) seq = seq / 2 / 128 * 128;
+    while (seq > 128 && share > 0 && static_cast<double>(q_bytes() + o_bytes() + 2 * kv_bytes()) > share) seq = seq / 2 / 128 * 128;
     scale = 1.0f / std::sqrt(static_cast<float>(kHeadDim));
     q = dev.alloc(q_bytes());
-    o = dev.alloc(q_bytes());
+    o = dev.alloc(o_bytes());
     k = dev.alloc(kv_bytes());
     v = dev.alloc(kv_bytes());
     totals = dev.alloc(2 * sizeof(uint64_t));
     auto s = dev.create_stream(false);
-    dev.fill_random(q.data(), q_bytes() / 2, DType::BF16, 1, *s);
-    dev.fill_random(k.data(), kv_bytes() / 2, DType::BF16, 2, *s);
-    dev.fill_random(v.data(), kv_bytes() / 2, DType::BF16, 3, *s);
+    dev.fill_random(q.data(), q_count(), dtype, 1, *s);
+    dev.fill_random(k.data(), kv_count(), dtype, 2, *s);
+    dev.fill_random(v.data(), kv_count(), dtype, 3, *s);
     dev.memset_async(totals.data(), 0, 2 * sizeof(uint64_t), *s);
     // the kernel's first launch (code object load, the one-block-per-CU
     // check) here, never inside a graph capture: one Q tile, counted nowhere
-    kernels::attention_fwd(q.data(), k.data(), v.data(), o.data(), nullptr, 1, 1, 1, 128, 128, scale, true, 0, 1,
-                           s->native());
+    launch(1, 1, 128, 0, 1, s->native(), nullptr, nullptr, nullptr);
     s->synchronize();
   }
   void task(Stream& s, uint64_t ticks, int grid, uint64_t* start, uint64_t* extra) {
-    kernels::attention_fwd(q.data(), k.data(), v.data(), o.data(), nullptr, 1, heads, kv_heads, seq, seq, scale, true,
-                           std::max<uint64_t>(ticks, 1), grid, s.native(), start, extra, totals.as<uint64_t>(), nullptr);
+    launch(heads, kv_heads, seq, std::max<uint64_t>(ticks, 1), grid, s.native(), start, extra, totals.as<uint64_t>());
   }
   // What the attention tasks computed so far (device totals: every launch and
   // every replay of a captured one adds to them) in the time they ran. A
@@ -195,6 +208,7 @@ struct AttnStandIn {
     a["kv_heads"] = kv_heads;
     a["head_dim"] = kHeadDim;
     a["causal"] = true;
+    a["dtype"] = dtype_name(dtype);
     a["grid"] = grid;
     a["kv_tile"] = kernels::kAttnKvTile;
     const double flops = 4.0 * 128 * kernels::kAttnKvTile * kHeadDim * static_cast<double>(t[0]);
@@ -232,7 +246,7 @@ class GpuCompute : public ComputeEngine {
     if (mode_ == ComputeMode::Attn) {
       // one block per CU too (attention.hip): hbm's grid rule
       grid_ = free_cus(shape, true);
-      attn_.setup(dev_, shape, memory_share(shape));
+      attn_.setup(dev_, shape, dtype_, memory_share(shape));
     }
     if (gemm_mode()) setup_deadline_state(shape);
     slice_us_ = mode_ == ComputeMode::Gemm ? choose_slice_us(shape) : 0.0;

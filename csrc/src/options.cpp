@@ -82,7 +82,7 @@ std::string usage(StrategyKind kind, const std::string& prog) {
      << "  --wire-dtype T         bf16 | fp16 | fp32 | fp8 (collective element type)\n"
      << "  --wire-quant Q         none | mxfp8: bf16 collectives are quantized block-wise (MXFP8 E4M3, 32 elements\n"
      << "                         per e8m0 scale) before the transport and dequantized after it (--wire-dtype bf16)\n"
-     << "  --compute-dtype T      auto | bf16 | fp8 (GEMM operand type for gemm/flops)\n"
+     << "  --compute-dtype T      auto | bf16 | fp8 (operand type of gemm/gemm-work/flops and of attn's Q, K, V)\n"
      << "  --schedule S           overlap (stream-ordered) | reference (blocking like DLNetBench)\n"
      << "  --tp-granularity G     microbatch | layer (hybrid_3d, hybrid_4d)\n"
      << "  --sequence-parallel    hybrid_3d/4d: each TP all-reduce becomes all-gather + reduce-scatter (Megatron-SP)\n"

@@ -91,6 +91,8 @@ def lib() -> ctypes.CDLL:
     L.dlnb_hbm_chunk_bytes.restype = c_size
     L.dlnb_attention_fwd.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
                                      c_dbl, c_int, c_int, c_vp, c_vp, c_vp, c_vp]
+    L.dlnb_attention_fwd_fp8.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float,
+                                         c_float, c_int, c_dbl, c_int, c_int, c_vp, c_vp, c_vp, c_vp]
     L.dlnb_attn_kv_tile.restype = c_int
     L.dlnb_stamp.argtypes = [c_vp, c_vp]
     L.dlnb_mx_wire_bytes.argtypes = [c_size]
